@@ -9,11 +9,20 @@ worst case), grad-accum 1. Random-init weights, synthetic data
 resident in HBM before the timed region.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--global-negatives]
+                       [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
 Prints ONE JSON line on rank 0. The default (c3, Mode R) is the headline line; --config c2 / c5 time
 BASELINE.json's other single-GPU-sized configurations with their own per-kernel fractions, and
 --global-negatives times Mode G (BASELINE c4: every rank contrasts its queries against the keys of
 all ranks, RCCL all-gather / reduce-scatter inside the head).
+
+A plain run sets up, warms up, times the K steps and prints the line (the per-kernel figures in it
+are read from events recorded inside those same steps). Everything that takes steps or work of its
+own -- the separate-frames and other-stream-mode timings, the serial-vs-concurrent bit-identity
+check, the reducer check at N > 1 and the CPU baseline -- runs only with --full.
+--dump-outputs DIR writes what the last timed step returned, and samples of the state it left, as
+DIR/<name>.npy (rank 0); inputs, weights and every random draw are seeded, so two builds run with
+the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -67,6 +76,12 @@ def parse():
                     help="BASELINE configuration (c3 = the headline; c2 / c5 = their own lines)")
     ap.add_argument("--global-negatives", action="store_true",
                     help="Mode G: contrast against the keys of every rank (BASELINE c4 at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: separate-frames and other-stream-mode "
+                         "timings, the serial-vs-concurrent bit-identity check, the reducer check (N > 1) "
+                         "and the CPU baseline (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (default: the config's)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-steps", type=int, default=3)
@@ -154,6 +169,33 @@ def kernel_report(timers):
     return rep
 
 
+DUMP_SAMPLE = 1 << 21   # elements sampled from each flat trainer buffer (8 MB as float32)
+
+
+def dump_outputs(path, out, trainer):
+    """--dump-outputs: what the last timed step handed its caller, one float32 / float64 .npy per name.
+    Every entry of the step's result dict (losses, gradient norms; the two heads' statistics as
+    vectors in their key order), and -- the step's other product being the trainer it updated -- a
+    fixed, seeded sample of the flat fp32 parameters and of AdamW's first moment (the running
+    gradient) after that step."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, torch.Tensor):
+            arrays[k] = v.detach().float().cpu().numpy()
+        else:   # LazyStats: a mapping of Python floats
+            arrays[k] = np.array([v[s] for s in v], dtype=np.float64)
+    space = trainer.space
+    idx = torch.randint(0, space.numel, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(97))
+    idx = idx.sort().values.to(space.flat_p.device)
+    arrays["params_sample"] = space.flat_p[idx].cpu().numpy()
+    arrays["adam_exp_avg_sample"] = space.exp_avg[idx].cpu().numpy()
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(arrays)
+
+
 def model_streams():
     """Does forward_triad run the audio / text backbones on their own streams (the headline mode)?"""
     from triad_amd.model import modality_streams_enabled
@@ -226,6 +268,8 @@ def main():
     # runtime kernel compilation on a fresh box.
     torch.backends.cudnn.benchmark = False
     torch.manual_seed(1234)
+    import numpy as np
+    np.random.seed(1234 + rank)   # SpecAugment masks (transformers draws them from numpy)
     model = MultiModalModel(audio_model_name=cfg["audio_model"], temperature=1.5, patch_sparsity_threshold=0.80,
                             patch_sparsity_weight=0.01, visual_dropout_prob=0.25, use_amp=True,
                             vit_arch=cfg["vit_arch"]).to(dev)
@@ -288,9 +332,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     loss = float(out["loss"])
+    if a.dump_outputs and rank == 0:   # before any --full leg steps the trainer further
+        names = dump_outputs(a.dump_outputs, out, trainer)
+        print(f"[bench] outputs of the last timed step: {len(names)} arrays in {a.dump_outputs}", file=sys.stderr,
+              flush=True)
     rep = kernel_report(timers)
     sep = None
-    if a.separate_steps > 0 and not a.separate_frames and shared:
+    if a.full and a.separate_steps > 0 and not a.separate_frames and shared:
         # the --separate-frames figure beside the headline: AV and TV frames encoded separately
         frames_sep = frames.roll(1, 0).contiguous()
 
@@ -316,7 +364,7 @@ def main():
             print(f"[bench] {a.separate_steps} separate-frames steps: {dts:.2f} s", file=sys.stderr, flush=True)
 
     rcheck = None
-    if world > 1 and trainer.reducer is not None:
+    if a.full and world > 1 and trainer.reducer is not None:
         # correctness gate of the overlapped gradient reduction: one more step with
         # every bucket's pre-reduction gradient snapshotted; after it the same buckets are
         # all-reduced again from the snapshots, one at a time with the device otherwise idle, and
@@ -329,7 +377,7 @@ def main():
             print(f"[bench] reducer check: {rcheck}", file=sys.stderr, flush=True)
 
     single = None
-    if a.single_stream_steps > 0:
+    if a.full and a.single_stream_steps > 0:
         # the same step in the other execution mode, reported beside the headline: the serial step
         # (one stream) beside the concurrent default (backbones on three streams + the dW side stream)
         from triad_amd import linear as _lin
@@ -472,13 +520,13 @@ def main():
             res["separate_frames"] = {"value": sep, "unit": "triples/s", "steps": a.separate_steps,
                                       "note": "AV and TV frame batches encoded separately, as the reference's "
                                               "two data loaders do (2x ViT work)"}
-        if world == 1 and a.stream_check and headline:
+        if a.full and world == 1 and a.stream_check and headline:
             del trainer, model
             torch.cuda.empty_cache()
             bit = stream_bit_identity(dev, frames, audio, text)
             res["stream_bit_identity"] = bit
             print(f"[bench] serial vs concurrent step at B={a.batch}: {bit}", file=sys.stderr, flush=True)
-        if world == 1 and not a.no_cpu_baseline and headline:
+        if a.full and world == 1 and not a.no_cpu_baseline and headline:
             from oracle import cpu_step
             # the threads this process may use: torch's intra-op pool honours OMP_NUM_THREADS (the GPU box
             # sets it to the job's CPU share; its affinity mask shows the whole machine, and oversubscribing

@@ -44,6 +44,8 @@ import torch
 import torch.nn as nn
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(OUT))   # tests/ (golden_io)
+from golden_io import save as _save  # noqa: E402  (one .npz, or several when it would pass 1 MiB)
 REF_SRC = "/root/reference/src"
 D = 512
 
@@ -99,8 +101,8 @@ def gen_av(ref_model, name, B, Na, Nv, temp, seed, nv_len=None):
     clip, tok = m.compute_all_similarities_av(A, V)
     total, ce, reg, smooth, stats = m.compute_contrastive_loss_av(clip, tok)
     total.backward()
-    np.savez_compressed(
-        os.path.join(OUT, name + ".npz"),
+    _save(
+        name,
         kind="av", A=_u16(A), V=_u16(V),
         nv_len=np.array(nv_len if nv_len is not None else [Nv] * B, np.int32),
         temp=np.float32(temp),
@@ -132,8 +134,8 @@ def gen_tv(ref_model, name, B, Nt, Nv, temp, seed, lens, thr=0.80, w=0.01, nv_le
     clip, tok = m.compute_all_similarities_tv(T, V, mask)
     total, stats = m.compute_contrastive_loss_tv(clip, tok)
     total.backward()
-    np.savez_compressed(
-        os.path.join(OUT, name + ".npz"),
+    _save(
+        name,
         kind="tv", T=_u16(T), V=_u16(V), mask=mask.numpy().astype(np.int64),
         nv_len=np.array(nv_len if nv_len is not None else [Nv] * B, np.int32),
         temp=np.float32(temp), thr=np.float64(thr), w=np.float64(w),
@@ -154,9 +156,9 @@ def gen_simmat(ref_model, name, B, N1, N2, temp, seed):
     f2 = _feats(g, (B, N2, D))
     m = _make_model(ref_model, temp)
     sim = m.compute_similarity_matrix(f1, f2)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), kind="simmat",
-                        f1=_u16(f1), f2=_u16(f2), temp=np.float32(temp),
-                        sim=sim.detach().numpy().astype(np.float32))
+    _save(name, kind="simmat",
+          f1=_u16(f1), f2=_u16(f2), temp=np.float32(temp),
+          sim=sim.detach().numpy().astype(np.float32))
     print(name, sim.shape)
 
 
@@ -171,9 +173,9 @@ def gen_dropout(ref_model, name, B, N, drop, seed):
     # Re-draw the identical mask from the same global RNG state (same call shape and dtype).
     torch.manual_seed(seed)
     keep = torch.bernoulli(torch.ones(B, N, dtype=x.dtype) * (1 - drop)).bool()
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), kind="dropout",
-                        x=_u16(x), keep=keep.numpy(), drop=np.float64(drop),
-                        out=_u16(out))
+    _save(name, kind="dropout",
+          x=_u16(x), keep=keep.numpy(), drop=np.float64(drop),
+          out=_u16(out))
     print(name, tuple(out.shape), keep.sum(1).tolist())
 
 
@@ -221,8 +223,8 @@ def gen_retrieval(ref_retrieval, name, kind, N, q_lens, k_lens, temp, seed, dup_
     r_qk = ref_retrieval.compute_recall_at_k(s_qk)
     r_kq = ref_retrieval.compute_recall_at_k(s_kq)
     ranks = lambda s: np.array([int(np.where(np.argsort(-s[i]) == i)[0][0]) for i in range(N)], np.int32)
-    np.savez_compressed(
-        os.path.join(OUT, name + ".npz"), kind="retrieval_" + kind, temp=np.float32(temp),
+    _save(
+        name, kind="retrieval_" + kind, temp=np.float32(temp),
         q=_u16(torch.cat(q)), q_len=np.array([len(x) for x in q], np.int32),
         k=_u16(torch.cat(k)), k_len=np.array([len(x) for x in k], np.int32),
         sim_qk=s_qk, sim_kq=s_kq, ranks_qk=ranks(s_qk), ranks_kq=ranks(s_kq),
@@ -245,8 +247,8 @@ def gen_znorm(name, B, T, seed, offset=0.0, scale=0.1):
     x = torch.randn(B, T, generator=g) * scale + offset
     y = fe(x, return_tensors="pt", sampling_rate=16000, padding=True,
            return_attention_mask=True).input_values.squeeze(0)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), kind="znorm", x=x.numpy().astype(np.float32),
-                        y=y.numpy().astype(np.float32))
+    _save(name, kind="znorm", x=x.numpy().astype(np.float32),
+          y=y.numpy().astype(np.float32))
     print(name, tuple(y.shape), float(y.mean()), float(y.std()))
 
 

@@ -22,6 +22,7 @@ OUT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(OUT))          # tests/ (retrieval_stub)
 sys.path.insert(0, "/root/reference/src")
 import retrieval as ref  # noqa: E402  (the reference module)
+import golden_io  # noqa: E402  (writes one .npz, or several when it would pass 1 MiB)
 from retrieval_stub import AVStubDataset, StubModel, TVStubDataset  # noqa: E402
 
 N_DATA, N_SUB, SEED = 24, 16, 7
@@ -81,7 +82,7 @@ def main():
         out["tv_keys"] = np.array(list(res_tv.keys()))
         out["tv_vals"] = np.array([float(x) for x in res_tv.values()], dtype=np.float64)
     out["av_paths"] = np.array(paths)
-    np.savez_compressed(os.path.join(OUT, "retrieval_e2e_n24.npz"), **out)
+    golden_io.save("retrieval_e2e_n24", **out)
     for k in ("av", "tv"):
         print(k, dict(zip(out[k + "_keys"], out[k + "_vals"])))
 

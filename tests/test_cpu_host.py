@@ -456,3 +456,44 @@ def test_bench_tracks_every_hot_path_entry_point():
     # the round-5 omission: the compact-tile dS patch is the backward's product form
     assert "triad_dS_patch_tiles" in bench.TRACKED and "triad_pairsim_fwd_multi" in bench.TRACKED
     assert not set(bench.TRACKED) & _lib.BACKBONE_ENTRY_POINTS
+
+
+def test_bench_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` asks for none of the legs beside the
+    headline; --full and --dump-outputs DIR are the options that add them."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs_writes_float_arrays_by_name(tmp_path):
+    """bench.dump_outputs: one float32 / float64 .npy per entry of the step's result (statistics
+    mappings as vectors in key order) plus the same seeded sample of the flat parameters and of
+    AdamW's first moment on every call, well under 64 MB in all."""
+    import types
+    import bench
+    from triad_amd.model import _AV_KEYS, LazyStats
+    n = 3 * bench.DUMP_SAMPLE + 11
+    space = types.SimpleNamespace(numel=n, flat_p=torch.arange(n, dtype=torch.float32),
+                                  exp_avg=-torch.arange(n, dtype=torch.float32))
+    out = {"loss": torch.tensor(2.5), "grad_norm_vit": torch.tensor(0.25, dtype=torch.bfloat16),
+           "av_stats": LazyStats(_AV_KEYS, torch.arange(8.0))}
+    trainer = types.SimpleNamespace(space=space)
+    names = bench.dump_outputs(str(tmp_path / "a"), out, trainer)
+    assert names == sorted(["loss", "grad_norm_vit", "av_stats", "params_sample", "adam_exp_avg_sample"])
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["loss"] == np.float32(2.5) and got["grad_norm_vit"] == np.float32(0.25)
+    assert got["av_stats"].tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+    p = got["params_sample"]
+    assert p.shape == (bench.DUMP_SAMPLE,) and (np.diff(p) >= 0).all() and 0 <= p[0] and p[-1] < n
+    assert p[-1] > 2.9 * bench.DUMP_SAMPLE   # drawn over the whole buffer, not its head
+    assert np.array_equal(got["adam_exp_avg_sample"], -p)
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    bench.dump_outputs(str(tmp_path / "b"), out, trainer)
+    assert np.array_equal(np.load(tmp_path / "b" / "params_sample.npy"), p)

@@ -281,7 +281,7 @@ def test_overlapped_bucket_reducer_averages_gradients(wire, skip):
 
 @pytest.mark.parametrize("wire,check", [("fp32", "clean"), ("bf16", "clean"), ("fp32", "perturbed")])
 def test_reducer_check_gate(wire, check):
-    """the reducer's correctness gate (bench.py --gpus N > 1 prints its result).
+    """the reducer's correctness gate (bench.py --full --gpus N > 1 prints its result).
     With `check` set for a step, every bucket's pre-reduction gradient is snapshotted, the same
     buckets are all-reduced again from the snapshots after backward, in the same order, and the
     two results are compared bit for bit (max over ranks): equal on a clean run (fp32 and bf16

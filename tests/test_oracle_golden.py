@@ -169,3 +169,31 @@ def test_near_ties_flags_exact_and_close_row_maxima():
     kr = (torch.randn(4, 60, 512, generator=g) * 0.58).double()
     tq3, tk3, _ = ref_cpu.near_ties(qr, kr, 1.5)
     assert float(tq3.float().mean()) < 0.02
+
+
+def test_fixture_files_stay_under_one_mib_and_large_ones_split_bit_exactly(tmp_path):
+    """No committed fixture file exceeds 1 MiB. golden_io.save spreads a larger fixture over
+    `<name>.npz` + `<name>.partK.npz`, and load returns the same arrays bit for bit (dtype, shape,
+    0-d and string entries included); a small fixture stays one plain .npz."""
+    import glob
+    import os
+    for p in glob.glob(os.path.join(G.GOLDEN, "*")):
+        assert os.path.getsize(p) <= 1 << 20, p
+    rng = np.random.default_rng(0)
+    big = {"kind": "av", "temp": np.float32(1.5), "total": np.float64(3.25),
+           "A": rng.integers(0, 1 << 16, (4, 199, 512), dtype=np.uint16),
+           "dA": rng.standard_normal((4, 199, 512)).astype(np.float32),
+           "keep": rng.random((3, 256)) < 0.5, "dA_len": np.arange(4, dtype=np.int32)}
+    G.save("big", out_dir=str(tmp_path), **big)
+    files = sorted(os.listdir(tmp_path))
+    assert files[0] == "big.npz" and len(files) > 1 and all(f.startswith("big.part") for f in files[1:])
+    assert all(os.path.getsize(tmp_path / f) <= 1 << 20 for f in files)
+    back = G.load("big", out_dir=str(tmp_path))
+    assert set(back) == set(big)
+    for k, v in big.items():
+        v = np.asarray(v)
+        assert back[k].dtype == v.dtype and back[k].shape == v.shape and back[k].tobytes() == v.tobytes(), k
+    small = {"kind": "tv", "x": np.arange(12.0).reshape(3, 4)}
+    G.save("small", out_dir=str(tmp_path), **small)
+    assert [f for f in os.listdir(tmp_path) if f.startswith("small")] == ["small.npz"]
+    assert np.array_equal(np.load(tmp_path / "small.npz")["x"], small["x"])

@@ -174,7 +174,7 @@ class GradBucketReducer:
         self.comm = torch.cuda.Stream(space.device) if self.cuda else None
         self.launched_in_backward = 0                           # overlap evidence (tests, logs)
         self._hooks = {}   # registered lazily: a frozen parameter (requires_grad False) takes no hook
-        # correctness gate (bench.py --gpus N > 1): with `check` set for a step, each
+        # correctness gate (bench.py --full --gpus N > 1): with `check` set for a step, each
         # bucket's local gradient is snapshotted right before its overlapped all-reduce, and after the
         # step the same buckets are all-reduced again from the snapshots in the same order with the
         # device otherwise idle; `check_result` compares the two bit for bit (max over ranks)
