@@ -63,7 +63,9 @@ int triad_pairsim_fwd(const void* Q, const void* K, int R, int R_pad, int Nq, in
  * exclusive prefix sum of nkb or nkb - 1 tiles per sample, nkb = Nk_pad / 32; a sample at index
  * >= 64 within a forward workgroup's key split stores all nkb), CT >= k_tiles[Bk]. The left-out
  * tile's S == 0 enters the row max in closed form. diagS (triad_pairsim_diag) needs the full
- * padded K: give it the problems with the padded K and k_tiles NULL. */
+ * padded K: give it the problems with the padded K and k_tiles NULL. A problem with diag, diagS
+ * and k_tiles all set is refused (TRIAD_EINVAL) by triad_pairsim_fwd_multi and triad_pairsim_diag
+ * alike: the diagonal pass would read the compact K past its end. */
 typedef struct triad_pairsim_problem {
   const void* Q;
   const void* K;
@@ -177,6 +179,9 @@ int triad_tile_gemm_packed16_slabs(const void* Dt, long long CT, int dk, const v
 
 /* C = alpha * op(A) . op(B): A [M][Kd] (a_kcontig=1) or [Kd][M] (0); B [N][Kd] (b_kcontig=1)
  * or [Kd][N] (0); C fp32 or bf16 (out_bf16). M, N multiples of 128, Kd of 64.
+ * Every GEMM entry point below returns TRIAD_EINVAL before any launch for: M, N or Kd <= 0 or not
+ * such multiples; lda or ldb not a multiple of 8; ldc < N; NULL A, B or C; A or B not 16-byte
+ * aligned (operands are fetched by 16-byte LDS-DMA). Rows of A may overlap (lda < Kd is allowed).
  * dQ = temp * dS . K and dK = temp * dS^T . Q of S = temp * Q K^T (model.py:387/505),
  * and the projection-head GEMMs (model.py:68/116/326). */
 int triad_gemm_bf16(const void* A, long long lda, int a_kcontig, const void* B, long long ldb, int b_kcontig,
@@ -197,7 +202,9 @@ int triad_gemm_bf16_bias_bf16(const void* A, long long lda, int a_kcontig, const
                               hipStream_t stream);
 
 /* Split-K GEMM (weight gradients of the projection heads, train.py:987 backward):
- * `splits` fp32 partial slabs [splits][M][N] in caller-owned `slabs`, then C = alpha * sum. */
+ * `splits` fp32 partial slabs [splits][M][N] in caller-owned `slabs`, then C = alpha * sum.
+ * 1 <= splits <= 65535, slabs and C not NULL, else TRIAD_EINVAL; a split that gets no k-steps
+ * (splits not dividing Kd / 64) writes a zero slab. */
 int triad_gemm_bf16_splitk(const void* A, long long lda, int a_kcontig, const void* B, long long ldb, int b_kcontig,
                            int M, int N, int Kd, int splits, const float* alpha, float* slabs, void* C,
                            int out_bf16, hipStream_t stream);

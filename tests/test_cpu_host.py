@@ -150,6 +150,71 @@ def test_pairsim_fwd_multi_rejects_bad_arguments():
     assert _lib.PairsimProblem.k_tiles.offset == 128
 
 
+def test_pairsim_entry_points_reject_a_diagonal_over_compact_keys():
+    """diag_sim addresses K in the padded layout (sample j at rows j * Nk_pad): with a compact key
+    set (k_tiles) it would read past K's end, so both entry points that launch it --
+    triad_pairsim_fwd_multi (diag && diagS) and triad_pairsim_diag -- return TRIAD_EINVAL (1001)
+    for such a problem, alone or as the second of two. No GPU needed: validation comes first."""
+    from triad_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build()
+    lib = _lib.load()
+    fake = 4096  # never dereferenced: validation fails first
+
+    def prob(k_tiles=None, st_part=None, dS=None):
+        return _lib.PairsimProblem(fake, fake, 200, 256, 50, 4, 4, 64, 60, fake, -60.0, 1, 0, fake, fake, fake,
+                                   fake, dS, 8, st_part, k_tiles)
+    for f in (lib.triad_pairsim_fwd_multi, lib.triad_pairsim_diag):
+        assert f((_lib.PairsimProblem * 1)(prob(k_tiles=fake)), 1, None) == 1001
+        assert f((_lib.PairsimProblem * 2)(prob(), prob(k_tiles=fake)), 2, None) == 1001
+        # the training form of the same problem (dS and its statistics present)
+        assert f((_lib.PairsimProblem * 1)(prob(k_tiles=fake, st_part=fake, dS=fake)), 1, None) == 1001
+
+
+def test_gemm_entry_points_reject_bad_arguments():
+    """gemm.hip launch() and the split-K entry validate before any launch (no GPU needed) ->
+    TRIAD_EINVAL (1001): sizes that are not positive multiples of the tile, row strides the 16-byte
+    LDS-DMA cannot take, ldc < N, NULL or misaligned operands, NULL slabs / C, a split count past
+    gridDim.y's limit, a form beyond 4. One assertion per rule and entry point; the first call of
+    each group is the valid base the others differ from in one argument."""
+    from triad_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build()
+    lib = _lib.load()
+    fake = 4096  # 16-byte aligned, never dereferenced: validation fails first
+
+    def form(A=fake, lda=128, B=fake, ldb=128, M=256, N=256, Kd=128, C=fake, ldc=256, form=1):
+        return lib.triad_gemm_bf16_form(A, lda, 1, B, ldb, 1, M, N, Kd, None, C, ldc, 0, form, None)
+
+    def bias(A=fake, lda=128, B=fake, ldb=128, M=256, N=256, Kd=128, C=fake, ldc=256):
+        return lib.triad_gemm_bf16_bias(A, lda, 1, B, ldb, 1, M, N, Kd, None, C, ldc, None)
+
+    def splitk(A=fake, lda=256, B=fake, ldb=256, M=256, N=256, Kd=128, splits=2, slabs=fake, C=fake, form=1):
+        return lib.triad_gemm_bf16_splitk_form(A, lda, 0, B, ldb, 0, M, N, Kd, splits, None, slabs, C, 0, form, None)
+
+    for f in (form, bias, splitk):
+        assert f(M=0) == 1001 and f(N=0) == 1001 and f(Kd=0) == 1001, f.__name__
+        assert f(M=-128) == 1001 and f(N=-128) == 1001 and f(Kd=-64) == 1001, f.__name__
+        assert f(A=None) == 1001, f.__name__
+        assert f(B=None) == 1001, f.__name__
+        assert f(C=None) == 1001, f.__name__
+        assert f(A=fake + 2) == 1001 and f(A=fake + 8) == 1001, f.__name__      # A not 16-byte aligned
+        assert f(B=fake + 2) == 1001 and f(B=fake + 8) == 1001, f.__name__      # B not 16-byte aligned
+    assert form(ldc=248) == 1001 and form(ldc=0) == 1001                        # ldc < N
+    assert bias(ldc=248) == 1001 and bias(ldc=0) == 1001
+    assert splitk(slabs=None) == 1001
+    assert splitk(splits=65536) == 1001 and splitk(splits=65536, form=1 | 8) == 1001   # past gridDim.y
+    assert splitk(splits=0) == 1001
+    # rules that existed and nothing pinned
+    assert form(M=200) == 1001                                                  # M % 128
+    assert form(N=200, ldc=200) == 1001                                         # N % 128
+    assert form(Kd=96) == 1001                                                  # Kd % 64
+    assert form(lda=132) == 1001 and form(ldb=132) == 1001                      # lda, ldb % 8
+    assert form(form=5) == 1001 and form(form=-1) == 1001                       # forms 0..4
+    assert bias(M=200) == 1001 and bias(Kd=96) == 1001 and bias(lda=132) == 1001
+    assert splitk(M=200) == 1001 and splitk(Kd=96) == 1001 and splitk(ldb=132) == 1001
+
+
 def test_packed_tile_gemm_and_patch_reject_bad_arguments():
     """The direct-B GEMM entry points, the dS patch and the loss head validate their shapes before
     launching anything (no GPU needed) -> TRIAD_EINVAL (1001)."""
@@ -288,6 +353,42 @@ def test_bias_grad_takes_only_the_lds_dma_form(rows, cols, view, monkeypatch):
     if rows:
         (_, (xp, r, c, ld, *_)), = [s for s in seen if s[0] == "triad_colsum_dma"]
         assert r == rows and c % 8 == 0 and ld % 8 == 0 and (xp.value or 0) % 16 == 0
+
+
+@pytest.mark.parametrize("case", ["tight", "column_slices", "O200", "K72", "shifted", "odd_stride", "no_tokens"])
+def test_weight_grad_routes_what_the_splitk_gemm_cannot_read_to_torch(case, monkeypatch):
+    """linear.weight_grad: host routing only (the C-ABI call is recorded, nothing runs). Tileable
+    widths with 16-byte aligned rows -- tight or column slices of wider tensors -- go to
+    triad_gemm_bf16_splitk_form with the operands' own row strides; a width that is not a multiple
+    of 128, a first element off a 16-byte boundary, a row stride that is not a multiple of 8 or an
+    empty token list never reach it (the entry point would refuse them) and give torch's dy^T x."""
+    from triad_amd import linear
+    seen = []
+    monkeypatch.setattr(linear, "call", lambda name, *a, **kw: seen.append((name, a)) or 0)
+    monkeypatch.setattr(linear, "stream_ptr", lambda *a: None)
+    g = torch.Generator().manual_seed(11)
+    M, O, K = (0 if case == "no_tokens" else 192), (200 if case == "O200" else 256), (72 if case == "K72" else 128)
+    wide_dy = torch.randn(M, 3 * O + 16, generator=g).to(torch.bfloat16)
+    wide_x = torch.randn(M, 3 * K + 16, generator=g).to(torch.bfloat16)
+    if case == "column_slices":
+        dy2, x2 = wide_dy[:, O:2 * O], wide_x[:, K:2 * K]
+    elif case == "shifted":
+        dy2, x2 = wide_dy[:, 1:O + 1], wide_x[:, :K]
+    elif case == "odd_stride":
+        dy2, x2 = wide_dy[:, :O].contiguous(), torch.randn(M, K + 4, generator=g).to(torch.bfloat16)[:, :K]
+    else:
+        dy2, x2 = wide_dy[:, :O].contiguous(), wide_x[:, :K].contiguous()
+    dw = linear.weight_grad(dy2, x2)
+    assert dw.shape == (O, K) and dw.dtype == torch.bfloat16
+    if case in ("tight", "column_slices"):
+        (name, a), = seen
+        assert name == "triad_gemm_bf16_splitk_form"
+        assert (a[0].value % 16, a[1], a[3].value % 16, a[4]) == (0, dy2.stride(0), 0, x2.stride(0))
+        assert a[6:9] == (O, K, M)
+    else:
+        assert not seen
+        ref = (dy2.double().t() @ x2.double())
+        assert torch.allclose(dw.double(), ref, rtol=2.0 ** -7, atol=1e-6 * M)
 
 
 def test_triad_linear_takes_every_token_count():

@@ -456,6 +456,8 @@ __global__ __launch_bounds__(512, 1) void gemm_w8_kernel(const bf16* __restrict_
 constexpr int kBigForm = 4;
 // form flag of the split-K entry points: the workgroups of one split all on one XCD (tile_split)
 constexpr int kXcdSplit = 8;
+// HIP's limit on gridDim.y, where the split index lives
+constexpr int kMaxGridY = 65535;
 
 
 template <bool AK, bool BK_, typename OutT>
@@ -464,8 +466,14 @@ int launch(const void* A, long long lda, const void* B, long long ldb, int M, in
            const void* bias = nullptr, int form = 0, int bias_bf16 = 0) {
   const int xsplit = (form & kXcdSplit) ? 1 : 0;
   form &= ~kXcdSplit;
+  if (M <= 0 || N <= 0 || Kd <= 0) return TRIAD_EINVAL;
   if (M % BM || N % BN || Kd % BK || lda % 8 || ldb % 8 || splits < 1) return TRIAD_EINVAL;
   if (xsplit && splits % 8) return TRIAD_EINVAL;
+  if (splits > kMaxGridY) return TRIAD_EINVAL;   // blockIdx.y is the split
+  if (!A || !B || !C || ldc < N) return TRIAD_EINVAL;
+  // every operand piece is a 16-byte LDS-DMA (glds16): with lda, ldb % 8 == 0 above, aligned bases
+  // make every piece aligned. (No lda >= Kd rule: the conv stack's A rows overlap, lda < Kd.)
+  if ((uintptr_t)A % 16 || (uintptr_t)B % 16) return TRIAD_EINVAL;
   const int kps = ((Kd / BK + splits - 1) / splits) * BK;
   // the 256-row ring pays off on long k loops or many row tiles (conv / projection GEMMs);
   // the short split-K weight-gradient loops keep the 128 x 128 form (measured, profiles/r01_dw_gemm_*.log)
@@ -575,6 +583,7 @@ int triad_gemm_bf16_splitk_form(const void* A, long long lda, int a_kcontig, con
                                 int b_kcontig, int M, int N, int Kd, int splits, const float* alpha, float* slabs,
                                 void* C, int out_bf16, int form, hipStream_t stream) {
   if ((form & ~kXcdSplit) < 0 || (form & ~kXcdSplit) > 4) return TRIAD_EINVAL;
+  if (!slabs || !C) return TRIAD_EINVAL;   // before the slab launch: nothing runs for a call that cannot finish
   const long long slab = (long long)M * N;
   int rc = TRIAD_EINVAL;
 #define TRIAD_GEMM_SK(AK, BKC)                                                                  \

@@ -652,6 +652,9 @@ int triad_pairsim_fwd_multi(const triad_pairsim_problem* problems, int n, hipStr
     if (p.dS && (p.CT < (p.k_tiles ? 1LL : (long long)p.Bk * (p.Nk_pad / 32)) || !p.st_part)) return TRIAD_EINVAL;
     if (!p.Q || !p.K || !p.temp || !p.rowmax || !p.argmax || !p.nn_part) return TRIAD_EINVAL;
     if (p.diag && p.diagS && (p.diag_off < 0 || p.diag_off + p.Bq > p.Bk)) return TRIAD_EINVAL;
+    // the diagonal pass this entry then launches (diag_sim) addresses K in the padded layout: a
+    // compact key set has fewer rows and would be read past its end (as triad_pairsim_diag below)
+    if (p.diag && p.diagS && p.k_tiles) return TRIAD_EINVAL;
     xb[i] = grid_for(p.R_pad, p.Bk, &jpw[i], &ys[i]);  // same decomposition as triad_pairsim_nparts
   }
   return triad_pairsim_fwd_multi_launch(problems, xb, ys, jpw, n, stream);

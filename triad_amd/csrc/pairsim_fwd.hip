@@ -31,6 +31,9 @@ constexpr int KT_ELEMS = 32 * D;
 #ifndef TRIAD_FWD_PF_AT
 #define TRIAD_FWD_PF_AT 9   // k-step after which the next tile's DMA is issued; -1: before the chain
 #endif                     // (round 6: 9 vs -1 AV -2.2 %, TV -2.5 %; 1-27 swept, profiles/r06_fwd_pf_at_ab.log)
+// the DMA is issued at `s == TRIAD_FWD_PF_AT` inside the k-step loop: a value at or past the step
+// count would never issue it, and the chain would read a stale ring slot
+static_assert(TRIAD_FWD_PF_AT < NS, "TRIAD_FWD_PF_AT must be a k-step of the chain (or negative)");
 #ifndef TRIAD_FWD_KPAD
 #define TRIAD_FWD_KPAD 1   // training ring: padded unswizzled rows, immediate ds_read offsets (A/B knob;
 #endif                   // AV -0.3 %, TV -0.6 %: profiles/r06_fwd_kpad_ab.log)
@@ -663,6 +666,7 @@ constexpr int NS16 = D / 32;  // 16 k-steps
 #ifndef TRIAD_FWD16_PF_AT
 #define TRIAD_FWD16_PF_AT 8   // eval body: k-step after which a tile pair's DMA is issued (A/B knob;
 #endif                      // 8 vs -1: AV -2.3 %, TV -1.3 %, 3 / 5 / 8 swept, profiles/r06_fwd_eval_pf_at_ab.log)
+static_assert(TRIAD_FWD16_PF_AT < NS16, "TRIAD_FWD16_PF_AT must be a k-step of the chain (or negative)");
 #ifndef TRIAD_FWD16_LDSPF
 #define TRIAD_FWD16_LDSPF 1
 #endif

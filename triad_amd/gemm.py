@@ -3,7 +3,9 @@ BLAS: F.linear under autocast (bf16 operands, fp32 accumulation, bias added befo
 rounding) and its input gradient dy . W. Measured on the c3 shapes at 790-940 TFLOP/s against
 rocBLAS's 300-790 (tools/gemm_backend_probe.py); hipBLASLt is not used (triad_amd/blas.py).
 Shapes the kernel does not tile (rows not a multiple of 128 -- small batches --, widths not a
-multiple of 128, contractions not a multiple of 64) go to torch, i.e. rocBLAS."""
+multiple of 128, contractions not a multiple of 64) go to torch, i.e. rocBLAS, and so do operands
+whose first element is not 16-byte aligned (a view at an odd offset into a wider buffer): the
+kernel fetches every operand by 16-byte LDS-DMA and the entry points reject such a pointer."""
 from __future__ import annotations
 
 import torch
@@ -14,6 +16,10 @@ from ._lib import call, ptr, stream_ptr
 _BF = torch.bfloat16
 def _ok(M, N, K):
     return M > 0 and M % 128 == 0 and N % 128 == 0 and K % 64 == 0
+
+
+def _aligned(*ts):
+    return all(t.data_ptr() % 16 == 0 for t in ts)
 
 
 def _rows(x):
@@ -34,6 +40,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None, meta
     if not (x2.is_cuda and _ok(M, N, K)):
         return F.linear(xb, wb, None if b is None else b.to(_BF))
     wc = wb if wb.is_contiguous() else wb.contiguous()
+    if not _aligned(x2, wc):
+        return F.linear(xb, wb, None if b is None else b.to(_BF))
     # the bias as autocast holds it (bf16), read by the epilogue as is: no cast launch when the
     # model's bias already is bf16 (the trainer's shadowed Linear layers, the projection heads)
     bias = None if b is None else b.detach().to(_BF).contiguous()
@@ -53,6 +61,8 @@ def mm(a: torch.Tensor, b: torch.Tensor, meta=None) -> torch.Tensor:
         return ab @ bb
     a2 = ab if ab.is_contiguous() else ab.contiguous()
     b2 = bb if bb.is_contiguous() else bb.contiguous()
+    if not _aligned(a2, b2):
+        return ab @ bb
     out = torch.empty(M, N, dtype=_BF, device=a2.device)
     call("triad_gemm_bf16_bias", ptr(a2), K, 1, ptr(b2), N, 0, M, N, K, None, ptr(out), N, stream_ptr(a2.device),
          meta=meta or dict(backbone=True, flops=2.0 * M * N * K))

@@ -61,11 +61,23 @@ def _form_splits(M, out_f, in_f):
     return 0, _splits(M, out_f, in_f)
 
 
+def _splitk_ok(t, width):
+    """May the split-K GEMM read the [tokens][width] bf16 operand t in place?"""
+    return (width % 128 == 0 and t.dtype == torch.bfloat16 and t.stride(1) == 1 and t.stride(0) % 8 == 0
+            and t.stride(0) >= width and t.data_ptr() % 16 == 0)
+
+
 def weight_grad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     """dW = dy2^T x2 (bf16 [O][K]) for dy2 [M][O], x2 [M][K] bf16 row-major (a token count that is
-    not a multiple of the GEMM's 64-deep k step is padded with zero rows, which add nothing)."""
+    not a multiple of the GEMM's 64-deep k step is padded with zero rows, which add nothing).
+    Widths the split-K GEMM does not tile (O or K not a multiple of 128), operands it cannot
+    fetch by 16-byte LDS-DMA (row stride not a multiple of 8 elements, first element not 16-byte
+    aligned, columns not contiguous) and an empty token list go to torch's bf16 matmul: fp32
+    accumulation and one bf16 rounding all the same, as the forward's fallback in gemm.linear."""
     M, O = dy2.shape
     K = x2.shape[1]
+    if not _splitk_ok(dy2, O) or not _splitk_ok(x2, K) or M == 0:
+        return dy2.t() @ x2
     if M % 64:
         Mp = (M + 63) // 64 * 64
         dy2 = torch.cat([dy2, dy2.new_zeros(Mp - M, O)])
