@@ -130,6 +130,37 @@ int triad_pairsim_dS(const void* Q, const void* K, int R, int R_pad, int Nq, int
                      const int* argmax, const float* dclip, const float* qw, const float* dSdiag,
                      const float* coef, void* dS, long long CT, double* dt_part, hipStream_t stream);
 
+/* fp32-accurate head (the reference's use_amp=False sims, model.py:483-488 / 603-608) in split-bf16
+ * arithmetic: an fp32 value x is the pair hi = bf16(x), lo = bf16(x - hi), and a product of two
+ * fp32 operands runs on the bf16 MFMA as lo.hi + hi.lo + hi.hi into one fp32 accumulator (small
+ * terms first; lo.lo dropped: |S_3 - S| ~ 1e-5 of a row's max). No atomics: bit-reproducible.
+ * Every entry point returns TRIAD_EINVAL before any launch for: a NULL required pointer; a bf16
+ * operand / dS pointer (or triad_split_pack's x) not 16-byte aligned; D != 512; R_pad not a
+ * multiple of 256 or < R; Nk_pad not a multiple of 32 or < Nk_eff; CT * 32 < Bk * Nk_pad or CT not
+ * a multiple of 4.
+ *
+ * triad_split_pack: x fp32 (B, N, 512) contiguous -> hi, lo bf16 [rows_alloc][512], sample b's
+ * tokens at rows b * N_pad .. b * N_pad + N - 1, every other row zero (queries: N_pad = N,
+ * rows_alloc = R_pad; keys: N_pad = Nk_pad, rows_alloc = C_alloc), in one pass.
+ * triad_pairsim_fwd_split: the outputs of triad_pairsim_fwd with dS == NULL and k_len == NULL
+ * (rowmax fp32, first argmax, nn_part[triad_pairsim_nparts(R_pad, Bk)] fp64, diagS fp32; diagS may
+ * be NULL), S in registers only.
+ * triad_pairsim_dS_split: triad_pairsim_dS with the three-term S; the fp32 dS is written as
+ * dS_hi = bf16(dS) and dS_lo = bf16(dS - dS_hi), both tiled [R_pad/32][CT][1024]. dQ / dK: per
+ * operand pair (dS_hi, B_hi), (dS_hi, B_lo), (dS_lo, B_hi) one triad_tile_gemm_slabs, reduced by
+ * triad_sum_slabs(alpha = temp, out_bf16 = 0). */
+int triad_split_pack(const float* x, int B, int N, int N_pad, long long rows_alloc, void* hi, void* lo,
+                     hipStream_t stream);
+int triad_pairsim_fwd_split(const void* Qhi, const void* Qlo, const void* Khi, const void* Klo, int R, int R_pad,
+                            int Nq, int Bq, int Bk, int Nk_pad, int Nk_eff, int D, const float* temp,
+                            float clamp_lo, int diag, int diag_off, float* rowmax, int* argmax, double* nn_part,
+                            float* diagS, hipStream_t stream);
+int triad_pairsim_dS_split(const void* Qhi, const void* Qlo, const void* Khi, const void* Klo, int R, int R_pad,
+                           int Nq, int Bq, int Bk, int Nk_pad, int Nk_eff, int D, const float* temp, float clamp_lo,
+                           int diag, int diag_off, const int* argmax, const float* dclip, const float* qw,
+                           const float* dSdiag, const float* coef, void* dS_hi, void* dS_lo, long long CT,
+                           double* dt_part, hipStream_t stream);
+
 /* Fast backward (only `total` differentiated): complete the forward's tiled unit l_nonneg
  * gradient (stored divided by su = |temp|, see triad_pairsim_fwd) in place, in the same units:
  * += ratio_max / su * dclip[i][j] * qw[r] at each row's argmax key (max backward,

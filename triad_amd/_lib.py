@@ -31,6 +31,11 @@ SIGNATURES = {
     "triad_losshead": [vp, i32, i32, vp, vp, i32, f64, vp, i32, f64, f32, vp, vp, vp, vp],
     "triad_pairsim_dS": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, f32, i32, i32, vp, vp, vp, vp, vp,
                          vp, i64, vp, vp],
+    "triad_split_pack": [vp, i32, i32, i32, i64, vp, vp, vp],
+    "triad_pairsim_fwd_split": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, f32, i32, i32, vp, vp,
+                                vp, vp, vp],
+    "triad_pairsim_dS_split": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, f32, i32, i32, vp, vp,
+                               vp, vp, vp, vp, vp, i64, vp, vp],
     "triad_dS_patch": [vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, f32, vp, i32, vp,
                        vp],
     "triad_dS_patch_tiles": [vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, f32, vp, i32,

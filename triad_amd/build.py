@@ -36,7 +36,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", CSRC, "-I
          "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] + os.environ.get("TRIAD_EXTRA_FLAGS", "").split()
 # per-file extras: the pipelined forward wants scalar f32 VALU beside its MFMAs (SLP-packed
 # v_pk_mul_f32 + operand moves cost more issue slots than two v_mul_f32 there)
-EXTRA = {"pairsim_fwd.hip": ["-fno-slp-vectorize"]}
+EXTRA = {"pairsim_fwd.hip": ["-fno-slp-vectorize"], "pairsim_split.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

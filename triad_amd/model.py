@@ -147,7 +147,12 @@ class ProjectionHead(nn.Module):
 
 
 def _project(emb, h):
-    """proj2(LN(proj1(h))) (model.py:68,116,201,326) via the fused HIP projection head."""
+    """proj2(LN(proj1(h))) (model.py:68,116,201,326) via the fused HIP projection head. An embedder
+    flagged reference_precision (MultiModalModel(use_amp=False): the reference then runs its
+    embedders in fp32) takes the plain fp32 torch chain instead -- the fused head rounds to bf16
+    even with autocast off; this path is not hot in that mode."""
+    if getattr(emb, "reference_precision", False):
+        return emb.projection2(emb.layer_norm(emb.projection1(h.float()))).float()
     return ops.projection_head(h, emb.projection1, emb.layer_norm, emb.projection2)
 
 
@@ -386,6 +391,9 @@ class MultiModalModel(nn.Module):
         self.patch_sparsity_threshold = patch_sparsity_threshold
         self.patch_sparsity_weight = patch_sparsity_weight
         self.use_amp = use_amp
+        if not use_amp:   # the reference's fp32 mode: fp32 projection heads, fp32 loss heads
+            for emb in (self.audio_embedder, self.text_embedder, self.visual_embedder):
+                emb.reference_precision = True
         self.amp_dtype = torch.bfloat16
         self.negatives_group = None  # process group for global negatives (SURVEY §8e Mode G)
         self.ds_budget = None        # bytes of tiled dS a head may materialise (None: ops.DS_BUDGET_BYTES)
@@ -402,10 +410,16 @@ class MultiModalModel(nn.Module):
         return ops.similarity_maps(feats1, feats2, self.temperature)
 
     # ---- fused training heads -------------------------------------------------------
+    def _head_precision(self):
+        """"bf16" under autocast (the product path); "fp32" for use_amp=False, as the reference
+        switches autocast off around its sims (model.py:483-488 / 603-608)."""
+        return "bf16" if getattr(self, "use_amp", True) else "fp32"
+
     def _av_head(self, audio_feats, visual_feats):
         losses, stats, clip = ops.contrastive_head(ops.AV, audio_feats, visual_feats, self.temperature,
                                                    group=self.negatives_group,
-                                                   ds_budget=getattr(self, "ds_budget", None))
+                                                   ds_budget=getattr(self, "ds_budget", None),
+                                                   precision=self._head_precision())
         return (losses[0], losses[1], losses[2], losses[3], LazyStats(_AV_KEYS, stats)), clip
 
     def _tv_head(self, text_feats, visual_feats, attention_mask):
@@ -413,7 +427,8 @@ class MultiModalModel(nn.Module):
                                                    q_mask=attention_mask, threshold=self.patch_sparsity_threshold,
                                                    sparsity_weight=self.patch_sparsity_weight,
                                                    group=self.negatives_group,
-                                                   ds_budget=getattr(self, "ds_budget", None))
+                                                   ds_budget=getattr(self, "ds_budget", None),
+                                                   precision=self._head_precision())
         return (losses[0], LazyStats(_TV_KEYS, stats)), clip
 
     # ---- materialising debug path (small B), reference model.py:370-593 -------
@@ -519,7 +534,8 @@ class MultiModalModel(nn.Module):
         (la, sa, _), (lt, st, _) = ops.contrastive_heads_av_tv(
             audio_feats, v_av, text_feats, v_tv, self.temperature, attention_mask,
             threshold=self.patch_sparsity_threshold, sparsity_weight=self.patch_sparsity_weight,
-            group=self.negatives_group, ds_budget=getattr(self, "ds_budget", None))
+            group=self.negatives_group, ds_budget=getattr(self, "ds_budget", None),
+            precision=self._head_precision())
         return (la[0], la[1], la[2], la[3], LazyStats(_AV_KEYS, sa)), (lt[0], LazyStats(_TV_KEYS, st))
 
     def forward(self, frames=None, audio=None, text_list=None):

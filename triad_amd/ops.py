@@ -695,8 +695,238 @@ class _ContrastiveHeadPair(torch.autograd.Function):
         return gqa, gka, gqt, gkt, gt, None, None, None, None, None
 
 
+# ----------------------------------------------------------------------------------------
+# fp32-accurate head (precision="fp32"): split-bf16 arithmetic, csrc/pairsim_split.hip
+# ----------------------------------------------------------------------------------------
+PRECISIONS = ("bf16", "fp32")
+
+
+def _check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+
+
+def split_pack(x: torch.Tensor, N_pad: int, rows_alloc: int):
+    """(B, N, 512) of any float dtype, read as fp32 -> (hi, lo): two zero-padded [rows_alloc][512]
+    bf16 operands with hi = bf16(x), lo = bf16(x - hi), sample b at rows b N_pad .. b N_pad + N - 1
+    (pack_queries' layout for N_pad = N, pack_keys' for N_pad = Nk_pad), in one pass."""
+    B, N, _ = x.shape
+    xc = x.detach().to(torch.float32).contiguous()
+    hi = torch.empty(rows_alloc, D, dtype=torch.bfloat16, device=x.device)
+    lo = torch.empty_like(hi)
+    call("triad_split_pack", ptr(xc), B, N, N_pad, rows_alloc, ptr(hi), ptr(lo), stream_ptr(x.device))
+    return hi, lo
+
+
+def _split_plan(g: Geometry, chunk: int):
+    """(key tiles per dS row panel, dQ split-K factor, dK split-K factor) at `chunk` key samples."""
+    nkb = g.Nk_pad // 32
+    ctc = _rup(chunk * nkb, 4)
+    sq = _gemm_splits(g.R_pad // 128, chunk * nkb, g.R_pad)
+    sk = _gemm_splits(ctc * 32 // 128, g.R_pad // 32, ctc * 32)
+    return ctc, sq, sk
+
+
+def split_working_bytes(g: Geometry, chunk: int) -> int:
+    """Device bytes the fp32 head's backward holds for dS at `chunk` key samples per chunk: the
+    chunk's TWO tiled bf16 dS buffers (hi, lo), the three-fold fp32 dQ slabs (three operand pairs x
+    split-K, plus the two running sums that carry dQ from chunk to chunk) and the three-fold dK
+    slabs of one chunk."""
+    ctc, sq, sk = _split_plan(g, chunk)
+    ds = 2 * (g.R_pad // 32) * ctc * 2048
+    acc = 0 if chunk >= g.Bk else 2
+    return ds + (3 * sq + acc) * g.R_pad * D * 4 + 3 * sk * ctc * 32 * D * 4
+
+
+def split_chunk_samples(g: Geometry, budget: int) -> int:
+    """Key samples per chunk of the fp32 head's (always recomputing) backward: the largest count
+    whose split_working_bytes fits `budget`. A budget below one key sample's working set is an
+    error, never silently exceeded."""
+    for chunk in range(g.Bk, 0, -1):
+        if split_working_bytes(g, chunk) <= budget:
+            return chunk
+    raise TriadError(f"ds_budget of {budget} bytes is below the fp32 head's working set for one key sample "
+                     f"({split_working_bytes(g, 1)} bytes)")
+
+
+def split_num_chunks(g: Geometry, budget: int) -> int:
+    """Number of key-sample chunks the fp32 head's backward runs for a geometry and dS budget."""
+    return -(-g.Bk // split_chunk_samples(g, budget))
+
+
+def split_recompute_backward(g: Geometry, Qs, Ks, temp, kind, argmax, dclip, qw, gdiag, coef, need_q, need_k, chunk,
+                             stream):
+    """recompute_backward in split-bf16 arithmetic. Per chunk of `chunk` key samples
+    triad_pairsim_dS_split recomputes S (three-term product) and writes the chunk's fp32 dS as
+    dS_hi + dS_lo; dQ and dK each come from THREE runs of the existing tile GEMM into unscaled fp32
+    slabs -- (dS_hi, B_lo), (dS_lo, B_hi), (dS_hi, B_hi), small terms first -- reduced by
+    triad_sum_slabs with alpha = temp straight to fp32. dQ is carried from chunk to chunk as an
+    unscaled fp32 running sum (two slabs, written alternately). Fixed order: bit-reproducible.
+    Qs / Ks: (hi, lo) of split_pack. Returns (dQ [R_pad][512] fp32 | None, dK [>= C_pad][512]
+    fp32 | None, dt_part fp64)."""
+    (Qhi, Qlo), (Khi, Klo) = Qs, Ks
+    dev = Qhi.device
+    f32 = torch.float32
+    nkb = g.Nk_pad // 32
+    nchunks = -(-g.Bk // chunk)
+    CT_c, sq, sk = _split_plan(g, chunk)
+    n_ds = (g.R_pad // 32) * CT_c * 1024
+    dS_hi = torch.empty(n_ds, dtype=torch.bfloat16, device=dev)
+    dS_lo = torch.empty(n_ds, dtype=torch.bfloat16, device=dev)
+    nq = g.R_pad * D
+    dQ = dK = q_slabs = k_slabs = None
+    if need_q:
+        # [running sum A][3 sq slabs][running sum B]: a chunk's slabs lie against the running sum they
+        # are added to, so one triad_sum_slabs over a contiguous range writes the other running sum
+        q_slabs = torch.empty(3 * sq + (2 if nchunks > 1 else 0), nq, dtype=f32, device=dev)
+        dQ = torch.empty(g.R_pad, D, dtype=f32, device=dev)
+    if need_k:
+        k_slabs = torch.empty(3 * sk * CT_c * 32 * D, dtype=f32, device=dev)
+        # a chunk writes whole 128-row panels: room for the last chunk's padded tail
+        dK = torch.empty(g.Bk * g.Nk_pad + CT_c * 32, D, dtype=f32, device=dev)
+    parts = []
+    for c in range(nchunks):
+        j0 = c * chunk
+        nc = min(chunk, g.Bk - j0)
+        nkt = nc * nkb
+        ctc = _rup(nkt, 4)
+        Kh, Kl = Khi[j0 * g.Nk_pad:], Klo[j0 * g.Nk_pad:]
+        if ctc > nkt:   # dK's last row panel reads the tail tiles: zeros, not stale memory
+            for b in (dS_hi, dS_lo):
+                b[:(g.R_pad // 32) * ctc * 1024].view(g.R_pad // 32, ctc, 1024)[:, nkt:].zero_()
+        dclip_c = dclip[:, j0:j0 + nc].contiguous() if nchunks > 1 else dclip
+        dt_c = torch.empty(call("triad_pairsim_nparts", g.R_pad, nc), dtype=torch.float64, device=dev)
+        fl = 2.0 * g.R * nc * g.Nk_eff * D
+        call("triad_pairsim_dS_split", ptr(Qhi), ptr(Qlo), ptr(Kh), ptr(Kl), g.R, g.R_pad, g.Nq, g.Bq, nc, g.Nk_pad,
+             g.Nk_eff, D, ptr(temp), CLAMP_LO[kind], 1, -j0, ptr(argmax[j0:]), ptr(dclip_c), ptr(qw), ptr(gdiag),
+             ptr(coef), ptr(dS_hi), ptr(dS_lo), ctc, ptr(dt_c), stream,
+             meta=dict(kind=kind, flops=0.0, recompute_flops=3.0 * fl))
+        parts.append(dt_c)
+        if need_q:
+            s = min(sq, nkt)
+            base = 1 if nchunks > 1 else 0
+            first = base if c & 1 or c == 0 else base + 3 * (sq - s)   # odd chunks add to A (slot 0), even ones to B
+            for i, (ds, B) in enumerate(((dS_hi, Kl), (dS_lo, Kh), (dS_hi, Kh))):
+                call("triad_tile_gemm_slabs", ptr(ds), ctc, 0, ptr(B), g.R_pad, nkt, s, ptr(q_slabs[first + i * s]),
+                     stream, meta=dict(kind=kind, flops=fl, what="dQ"))
+            if nchunks == 1:
+                call("triad_sum_slabs", ptr(q_slabs[first]), 3 * s, nq, ptr(temp), 0, ptr(dQ), stream)
+            elif c == 0:
+                call("triad_sum_slabs", ptr(q_slabs[first]), 3 * s, nq, None, 0, ptr(q_slabs[0]), stream)
+            elif c & 1:   # A + slabs -> B
+                call("triad_sum_slabs", ptr(q_slabs[0]), 3 * s + 1, nq, None, 0, ptr(q_slabs[3 * sq + 1]), stream)
+            else:         # slabs + B -> A
+                call("triad_sum_slabs", ptr(q_slabs[first]), 3 * s + 1, nq, None, 0, ptr(q_slabs[0]), stream)
+        if need_k:
+            Mk = ctc * 32
+            s = min(sk, g.R_pad // 32)
+            nk = Mk * D
+            for i, (ds, B) in enumerate(((dS_hi, Qlo), (dS_lo, Qhi), (dS_hi, Qhi))):
+                call("triad_tile_gemm_slabs", ptr(ds), ctc, 1, ptr(B), Mk, g.R_pad // 32, s, ptr(k_slabs[i * s * nk:]),
+                     stream, meta=dict(kind=kind, flops=fl, what="dK"))
+            call("triad_sum_slabs", ptr(k_slabs), 3 * s, nk, ptr(temp), 0, ptr(dK[j0 * g.Nk_pad:]), stream)
+    if need_q and nchunks > 1:
+        last = 3 * sq + 1 if (nchunks - 1) & 1 else 0
+        call("triad_sum_slabs", ptr(q_slabs[last]), 1, nq, ptr(temp), 0, ptr(dQ), stream)
+    return dQ, dK, torch.cat(parts) if len(parts) > 1 else parts[0]
+
+
+class _ContrastiveHeadFp32(torch.autograd.Function):
+    """_ContrastiveHead at the reference's fp32 precision (use_amp=False, model.py:483-488 /
+    603-608): the features are read as fp32 and every product with them -- S in the forward, the
+    recomputed S, dQ and dK in the backward -- runs in split-bf16 arithmetic (pairsim_split.hip),
+    so nothing is rounded to bf16. Local negatives only. The backward is always the recompute
+    form, in key-sample chunks within ds_budget; gradients come back in the inputs' dtypes.
+    Outputs as _ContrastiveHead."""
+
+    @staticmethod
+    def forward(ctx, q, k, temperature, kind, q_mask, thr, w_sparse, ds_budget):
+        _check_device(q, k, temperature, q_mask)
+        Bq, Nq, dq = q.shape
+        Bl, Nk, dk = k.shape
+        if dq != D or dk != D:
+            raise TriadError(f"feature dim must be {D}")
+        if Bq != Bl:
+            raise TriadError("query and key batches must match")
+        if Bq < 2:
+            raise TriadError("batch size must be >= 2 (no negatives for B == 1)")
+        dev = q.device
+        st = stream_ptr(dev)
+        h = _Head()
+        h.kind, h.group, h.W, h.rank, h.Nk, h.Bg = kind, None, 1, 0, Nk, Bq
+        h.g = g = Geometry(Bq, Nq, Bq, Nk)
+        budget = _default_budget(dev) if ds_budget is None else int(ds_budget)
+        h.chunk = split_chunk_samples(g, budget)
+        Qs = split_pack(q, Nq, g.R_pad)
+        Ks = split_pack(k, g.Nk_pad, g.C_alloc)
+        h.Qb = Qs[0]
+        h.temp = temperature.detach().reshape(1).to(torch.float32).contiguous()
+        h.nparts = call("triad_pairsim_nparts", g.R_pad, g.Bk)
+        h.rowmax = torch.empty(g.Bk, g.R_pad, dtype=torch.float32, device=dev)
+        h.argmax = torch.empty(g.Bk, g.R_pad, dtype=torch.int32, device=dev)
+        h.nn_part = torch.empty(h.nparts, dtype=torch.float64, device=dev)
+        h.diagS = torch.empty(g.Bq, g.Nq, g.Nk_pad, dtype=torch.float32, device=dev)
+        fl = 2.0 * g.R * g.Bk * g.Nk_eff * D
+        call("triad_pairsim_fwd_split", ptr(Qs[0]), ptr(Qs[1]), ptr(Ks[0]), ptr(Ks[1]), g.R, g.R_pad, g.Nq, g.Bq,
+             g.Bk, g.Nk_pad, g.Nk_eff, D, ptr(h.temp), CLAMP_LO[kind], 1, 0, ptr(h.rowmax), ptr(h.argmax),
+             ptr(h.nn_part), ptr(h.diagS), st, meta=dict(kind=kind, flops=3.0 * fl, grid=h.nparts * 256))
+        losses, stats, clip = _head_end(h, q_mask, thr, w_sparse, st)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(*Qs, *Ks, h.argmax, h.dclip, h.qw, h.gdiag, h.temp)
+        ctx.head = (g, kind, h.n_el, h.w_sparse, h.chunk, q.dtype, k.dtype, temperature.dtype, Nk)
+        ctx.mark_non_differentiable(stats, clip)
+        ctx.set_materialize_grads(False)
+        return losses[0], losses[1], losses[2], losses[3], stats, clip
+
+    @staticmethod
+    def backward(ctx, g_total, g_ce, g_reg, g_aux, g_stats, g_clip):
+        if g_total is None and g_ce is None and g_reg is None and g_aux is None:
+            return (None,) * 8
+        Qhi, Qlo, Khi, Klo, argmax, dclip, qw, gdiag, temp = ctx.saved_tensors
+        g, kind, n_el, w_sparse, chunk, q_dtype, k_dtype, t_dtype, Nk = ctx.head
+        needs = ctx.needs_input_grad[:3]
+        dev = Qhi.device
+        st = stream_ptr(dev)
+        f32 = torch.float32
+        zero = torch.zeros((), dtype=f32, device=dev)
+        gt_, gc_, gr_, ga_ = [zero if x is None else x.to(f32) for x in (g_total, g_ce, g_reg, g_aux)]
+        # the coefficients of _head_backward's recompute branch
+        c_ce = gt_ + gc_
+        c_reg = gt_ + gr_
+        c_nn = c_reg * (0.15 * 2.0 / n_el)
+        if kind == AV:
+            c_diag = 0.01 * (c_reg + ga_)
+            c_cal = 20.0 * c_reg
+        else:
+            c_diag = w_sparse * c_reg + ga_
+            c_cal = torch.zeros_like(c_reg)
+        coef = torch.stack([c_ce, c_nn, c_diag, c_cal]).contiguous()
+        dQ, dK, dt_part = split_recompute_backward(g, (Qhi, Qlo), (Khi, Klo), temp, kind, argmax, dclip, qw, gdiag,
+                                                   coef, needs[0], needs[1], chunk, st)
+        gq = gk = gt = None
+        if dQ is not None:
+            gq = dQ[:g.R].view(g.Bq, g.Nq, D).to(q_dtype)
+        if dK is not None:
+            gk = dK[:g.Bk * g.Nk_pad].view(g.Bk, g.Nk_pad, D)[:, :Nk].to(k_dtype)
+        if needs[2]:
+            w = torch.stack([torch.ones_like(c_ce), zero, zero, c_cal]).contiguous()
+            dt = torch.empty(1, dtype=f32, device=dev)
+            call("triad_dtemp_finalize", ptr(dt_part), dt_part.numel(), None, 0, None, 0, ptr(temp), ptr(w),
+                 1 if kind == AV else 0, ptr(dt), st)
+            gt = dt.reshape(()).to(t_dtype)
+        return gq, gk, gt, None, None, None, None, None
+
+
+def _head_fp32(kind, q, k, temperature, q_mask, threshold, sparsity_weight, group, ds_budget):
+    if group is not None:
+        raise TriadError("precision='fp32' runs local negatives only: global negatives (group=...) are built for "
+                         "the bf16 path alone")
+    o = _ContrastiveHeadFp32.apply(q, k, temperature, kind, q_mask, threshold, sparsity_weight, ds_budget)
+    return (o[0], o[1], o[2], o[3]), o[4], o[5]
+
+
 def contrastive_head(kind, q, k, temperature, q_mask=None, threshold=0.0, sparsity_weight=0.0, group=None,
-                     ds_budget=None):
+                     ds_budget=None, precision="bf16"):
     """Fused similarity + aggregation + InfoNCE + regularisers.
 
     kind AV: q = audio feats (B,Na,512), k = visual feats (B,Nv,512) (model.py:470-472)
@@ -708,17 +938,29 @@ def contrastive_head(kind, q, k, temperature, q_mask=None, threshold=0.0, sparsi
     ds_budget: bytes of tiled dS the training forward may materialise (default: a quarter of the
     device's HBM, at most 64 GiB); above it the backward recomputes S in key-sample chunks of at
     most that size (recompute_backward). The c4 per-rank shape (256 x 2048 samples) needs 47 GB.
+    precision: "bf16" (the product path: features rounded to bf16, bf16 dS and gradients) or "fp32"
+    (the reference's use_amp=False arithmetic: features read as fp32, split-bf16 products, fp32
+    gradients; local negatives only; the backward always recomputes S, in chunks whose working set
+    -- split_working_bytes -- fits ds_budget).
     """
+    _check_precision(precision)
+    if precision == "fp32":
+        return _head_fp32(kind, q, k, temperature, q_mask, threshold, sparsity_weight, group, ds_budget)
     total, ce, reg, aux, stats, clip = _ContrastiveHead.apply(q, k, temperature, kind, q_mask, threshold,
                                                               sparsity_weight, group, ds_budget)
     return (total, ce, reg, aux), stats, clip
 
 
 def contrastive_heads_av_tv(audio, visual_av, text, visual_tv, temperature, text_mask, threshold=0.0,
-                            sparsity_weight=0.0, group=None, ds_budget=None):
+                            sparsity_weight=0.0, group=None, ds_budget=None, precision="bf16"):
     """Both heads of the tri-modal step with one similarity-forward launch: equal to
     contrastive_head(AV, audio, visual_av, ...) and contrastive_head(TV, text, visual_tv, ...).
-    Returns ((losses, stats, clip) of AV, (losses, stats, clip) of TV)."""
+    Returns ((losses, stats, clip) of AV, (losses, stats, clip) of TV).
+    precision="fp32": the two single fp32 heads one after the other (no fused launch)."""
+    _check_precision(precision)
+    if precision == "fp32":
+        return (_head_fp32(AV, audio, visual_av, temperature, None, 0.0, 0.0, group, ds_budget),
+                _head_fp32(TV, text, visual_tv, temperature, text_mask, threshold, sparsity_weight, group, ds_budget))
     o = _ContrastiveHeadPair.apply(audio, visual_av, text, visual_tv, temperature, text_mask, threshold,
                                    sparsity_weight, group, ds_budget)
     return ((o[0], o[1], o[2], o[3]), o[4], o[5]), ((o[6], o[7], o[8], o[9]), o[10], o[11])
