@@ -215,6 +215,49 @@ def test_gemm_entry_points_reject_bad_arguments():
     assert splitk(M=200) == 1001 and splitk(Kd=96) == 1001 and splitk(ldb=132) == 1001
 
 
+def test_vit_row_entry_points_reject_bad_arguments():
+    """The LoRA row kernels (csrc/lora.hip) and the residual + LayerNorm passes (csrc/resid_ln.hip)
+    validate before any launch (no GPU needed) -> TRIAD_EINVAL (1001). One assertion per rule; each
+    helper's defaults are a valid call the others differ from in one argument."""
+    from triad_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libtriad_hip.so is not built")
+    lib = _lib.load()
+    fake = 4096  # 16-byte aligned, never dereferenced: validation fails first
+
+    def rows_nt(ldx=768, M=64, K=768, J=8):
+        return lib.triad_rows_nt(fake, ldx, M, K, fake, J, fake, None)
+
+    def update(ldy=768, M=64, O=768):
+        return lib.triad_lora_update(fake, ldy, M, O, fake, fake, None)
+
+    def tn(ldy=768, M=64, O=768, Wt=fake, dt=fake):
+        return lib.triad_lora_tn(fake, ldy, M, O, fake, Wt, dt, 1.0, fake, fake, None)
+
+    def fwd(M=64, D=768):
+        return lib.triad_addln_fwd(fake, fake, fake, fake, fake, 1e-6, M, D, fake, fake, 0, fake, fake, None)
+
+    def bwd(M=64, D=768):
+        return lib.triad_addln_bwd(fake, 0, fake, fake, fake, fake, fake, fake, M, D, fake, fake, None)
+
+    assert rows_nt(K=80, ldx=80) == 1001                                        # K % 32
+    assert rows_nt(J=0) == 1001 and rows_nt(J=17) == 1001                       # 1 <= J <= 16
+    assert rows_nt(ldx=760) == 1001 and rows_nt(ldx=772) == 1001                # ldx < K, ldx % 8
+    assert rows_nt(M=0) == 1001 and rows_nt(M=-64) == 1001
+    assert update(O=100, ldy=104) == 1001                                       # O % 8
+    assert update(ldy=760) == 1001 and update(ldy=772) == 1001                  # ldy < O, ldy % 8
+    assert update(M=0) == 1001
+    assert tn(O=384, ldy=384) == 1001                                           # O % 256
+    for nc in (5, 7, 10, 11, 13):                                               # no instance for these O / 256
+        assert tn(O=256 * nc, ldy=256 * nc) == 1001, nc
+    assert tn(dt=None) == 1001                                                  # Wt without dt
+    assert tn(ldy=760) == 1001 and tn(ldy=772) == 1001                          # ldy < O, ldy % 8
+    assert tn(M=0) == 1001
+    for f in (fwd, bwd):
+        assert f(D=800) == 1001 and f(D=1792) == 1001 and f(D=0) == 1001, f.__name__   # D % 256, D <= 1536
+        assert f(M=0) == 1001 and f(M=-4) == 1001, f.__name__
+
+
 def test_packed_tile_gemm_and_patch_reject_bad_arguments():
     """The direct-B GEMM entry points, the dS patch and the loss head validate their shapes before
     launching anything (no GPU needed) -> TRIAD_EINVAL (1001)."""

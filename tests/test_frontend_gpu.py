@@ -103,10 +103,21 @@ def test_hubert_pos_conv_matches_transformers(C, G, T):
 
 @pytest.mark.parametrize("M,K,O", [(66 * 261, 768, 2304), (5 * 37, 768, 768), (3, 384, 1152), (1001, 1024, 3072),
                                    (33, 768, 768), (256 * 261, 768, 2304)])
-def test_lora_linear_matches_reference_chain(M, K, O):
+def test_lora_linear_matches_reference_chain(monkeypatch, M, K, O):
     """ViT LoRA (triad_amd.vit._LoRALinear: rows_nt / lora_update / lora_tn HIP kernels + one base GEMM and an
-    in-place rank-8 update) against the reference chain base(x) + B(A(x)) * s under bf16 autocast."""
+    in-place rank-8 update) against the reference chain base(x) + B(A(x)) * s under bf16 autocast.
+    (3, 384, 1152) is the fallback case: those widths are outside the kernels' set, LoRALinear runs the
+    PyTorch chain itself and must make no HIP call; every other case must make the fast path's five
+    (tests/test_vit_rows_conformance_gpu.py checks the kernels themselves against fp64)."""
+    from triad_amd import vit as V
     from triad_amd.vit import LoRALinear
+    seen, real = {}, V.call
+
+    def counting(name, *a, **k):
+        if name != "triad_lora_tn_blocks":
+            seen[name] = seen.get(name, 0) + 1
+        return real(name, *a, **k)
+    monkeypatch.setattr(V, "call", counting)
     torch.manual_seed(M)
     base = torch.nn.Linear(K, O).to(dev)
     base.weight.data = base.weight.data.to(torch.bfloat16)
@@ -130,6 +141,7 @@ def test_lora_linear_matches_reference_chain(M, K, O):
     assert _rel(dx, rx) < 2e-2
     assert _rel(dA, gA) < 2e-2
     assert _rel(dB, gB) < 2e-2
+    assert seen == ({} if (K, O) == (384, 1152) else {"triad_rows_nt": 1, "triad_lora_update": 2, "triad_lora_tn": 2})
 
 
 def test_vit_fused_residual_ln_matches_unfused(monkeypatch):

@@ -154,13 +154,9 @@ __global__ __launch_bounds__(512, 2) void lora_tn_kernel(const bf16* __restrict_
   const int ntiles = (M + 31) / 32;
   for (int tt = tile0; tt < min(ntiles, tile0 + tiles_per_block); ++tt) {
     const int m0 = tt * 32;
-    // T tile [32][16] (rank padded with zeros)
-    if (tid < 64) {
-      const int r = tid >> 1, half = tid & 1;
-      bf16x8 v = {};
-      if (half == 0 && m0 + r < M) v = *(const bf16x8*)(T + (long long)(m0 + r) * TJ);
-      *(bf16x8*)(tbuf + r * 16 + half * 8) = v;
-    }
+    // T tile [32][16] (rank padded with zeros): loaded here, stored to tbuf inside chunk 0's barrier pair
+    bf16x8 tv = {};
+    if (tid < 64 && (tid & 1) == 0 && m0 + (tid >> 1) < M) tv = *(const bf16x8*)(T + (long long)(m0 + (tid >> 1)) * TJ);
     // this thread's two 16-B pieces of a chunk: rows (tid >> 5) and +16, 16-B column (tid & 31)
     const int pr = tid >> 5, pc = tid & 31;
     auto ld = [&](int c, int rr) __attribute__((always_inline)) -> bf16x8 {
@@ -171,7 +167,8 @@ __global__ __launch_bounds__(512, 2) void lora_tn_kernel(const bf16* __restrict_
     f32x4 dacc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      __syncthreads();  // previous chunk's LDS reads done (and tbuf written, for c == 0)
+      __syncthreads();  // every wave's reads of ybuf (previous chunk) and of tbuf (previous tile) are done
+      if (c == 0 && tid < 64) *(bf16x8*)(tbuf + (tid >> 1) * 16 + (tid & 1) * 8) = tv;
       *(bf16x8*)(ybuf + tn_off(pr, pc * 8)) = nx0;
       *(bf16x8*)(ybuf + tn_off(pr + 16, pc * 8)) = nx1;
       if (c + 1 < nch) { nx0 = ld(c + 1, pr); nx1 = ld(c + 1, pr + 16); }

@@ -14,6 +14,15 @@
 
 namespace {
 
+// x + g * y as two separately rounded operations, bit for bit torch's unfused fp32 chain. The
+// toolchain's __fmul_rn / __fadd_rn are plain * and +, which hipcc's default -ffp-contract=fast
+// fused into one fma (tests/test_vit_rows_conformance_gpu.py::test_addln_forward found it).
+__device__ __forceinline__ float add_scaled_unfused(float x, float g, float y) {
+#pragma clang fp contract(off)
+  const float p = g * y;
+  return x + p;
+}
+
 template <int NB>  // NB = D / 256
 __device__ __forceinline__ void row_stats(const float (&v)[NB][4], int D, float eps, float& mean, float& rstd) {
   float s = 0.f;
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(256) void addln_fwd_kernel(const float* __restrict_
       const bf16x4 yv = *(const bf16x4*)(y + row * D + c0);
       const f32x4 gv = *(const f32x4*)(g + c0);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) v[i][c] = __fadd_rn(xv[c], __fmul_rn(gv[c], (float)yv[c]));  // x + (g * y), unfused
+      for (int c = 0; c < 4; ++c) v[i][c] = add_scaled_unfused(xv[c], gv[c], (float)yv[c]);
       *(f32x4*)(xn + row * D + c0) = (f32x4){v[i][0], v[i][1], v[i][2], v[i][3]};
     } else {
 #pragma unroll

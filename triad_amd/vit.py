@@ -94,6 +94,17 @@ def lora_linear(x, w, b, A, B, scaling):
     return _LoRALinear.apply(x, w, b, A, B, scaling)
 
 
+# widths triad_lora_tn has an instance for (csrc/lora.hip TN_CASE: O / 256 of dB, K / 256 of dA)
+_LORA_TN_WIDTHS = frozenset(256 * n for n in (1, 2, 3, 4, 6, 8, 9, 12))
+
+
+def lora_hip_shapes(K, O, r):
+    """Whether _LoRALinear's kernels take a Linear(K, O) with rank r: forward AND backward. The
+    backward runs triad_lora_tn over dy (width O) and over x (width K), which exists only for
+    the widths above; triad_rows_nt needs K % 32 == 0; the kernels are built for rank 8."""
+    return r == 8 and K % 32 == 0 and K in _LORA_TN_WIDTHS and O in _LORA_TN_WIDTHS
+
+
 class LoRALinear(nn.Module):
     """y = base(x) + (alpha/r) * B(A(x)); base frozen by the caller, B zero-initialised."""
 
@@ -111,8 +122,8 @@ class LoRALinear(nn.Module):
 
     def forward(self, x):
         if x.is_cuda and torch.is_autocast_enabled("cuda") and not self.base.weight.requires_grad \
-                and (self.base.bias is None or not self.base.bias.requires_grad) and self.lora_A.shape[0] == 8 \
-                and self.lora_A.shape[1] % 256 == 0 and self.lora_B.shape[0] % 256 == 0:
+                and (self.base.bias is None or not self.base.bias.requires_grad) \
+                and lora_hip_shapes(self.lora_A.shape[1], self.lora_B.shape[0], self.lora_A.shape[0]):
             return lora_linear(x, self.base.weight, self.base.bias, self.lora_A, self.lora_B, self.scaling)
         return self.base(x) + F.linear(F.linear(x, self.lora_A), self.lora_B) * self.scaling
 
