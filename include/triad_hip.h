@@ -426,7 +426,14 @@ int triad_posconv_dw(const void* x, const void* dy, int B, int T, int C, int gro
  * 218-227; no dropout, no mask): O = softmax(Q K^T * scale) V per (sample, head), head dim D = 64,
  * N <= 320. Tensors are (B, N, H, 64) bf16 in memory with the head dim contiguous: element
  * (b, n, h, c) at b*sB + n*sN + h*64 + c. lse: [B*H][N] f32 log-sum-exp (forward output, backward
- * input); delta: [B*H][N] f32 scratch. */
+ * input); delta: [B*H][N] f32 rowsum(dO * O) (backward output: the dq kernel writes it, the dk / dv
+ * kernel reads it).
+ * TRIAD_EINVAL before any launch (here and in the _dropout forms) for: B, H or N <= 0, N > 320,
+ * D != 64, B*H > 65535 (one grid row per (sample, head)); a scale that is not finite or <= 0 (the
+ * row max is taken over the unscaled scores); a null or not 16-byte aligned q, k, v, out, o, dout,
+ * dq, dk or dv; an sB or sN that is not a multiple of 8 elements (rows are read and written as
+ * 16- and 8-byte vectors); a null lse, or a null delta in the backward; p outside [0, 1); one of
+ * wq, wk null and the other not. */
 int triad_attn_fwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
                    const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D, float scale, void* out,
                    long long out_sB, long long out_sN, float* lse, hipStream_t stream);

@@ -20,10 +20,17 @@ from ._lib import call, ptr, stream_ptr
 
 HEAD_DIM = 64
 MAX_TOKENS = 320
+MAX_SEQUENCES = 65535   # B * H: one grid row per (sample, head)
 
 
-def supported(x: torch.Tensor, n: int, head_dim: int) -> bool:
-    return x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and 0 < n <= MAX_TOKENS
+def supported(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int = 1) -> bool:
+    """What the entry points accept (they return TRIAD_EINVAL otherwise): bf16 on the device, head
+    dim 64, 1 .. 320 tokens, at most 65535 (sample, head) sequences, a finite scale > 0 (None = the
+    default 1 / sqrt(head dim)). The kernels take the row max of the unscaled scores."""
+    if scale is not None and not (math.isfinite(scale) and scale > 0.0):
+        return False
+    return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and 0 < n <= MAX_TOKENS
+            and 0 < sequences <= MAX_SEQUENCES)
 
 
 def _rows(t):
@@ -32,8 +39,12 @@ def _rows(t):
 
 
 def _as_bnhd(t):
-    if t.stride(3) != 1 or t.stride(2) != HEAD_DIM:
-        t = t.contiguous()
+    """t as the kernels read it: head dim contiguous, heads adjacent, and -- for their 16-byte
+    accesses -- a 16-byte aligned base with sB and sN multiples of 8 elements. Anything else is
+    copied."""
+    if (t.stride(3) != 1 or t.stride(2) != HEAD_DIM or t.stride(0) % 8 or t.stride(1) % 8
+            or t.data_ptr() % 16):
+        t = t.clone(memory_format=torch.contiguous_format)   # (.contiguous() keeps an offset view as it is)
     return t
 
 
@@ -110,7 +121,10 @@ class _AttentionQKV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, heads, scale, p=0.0):
         B, N, C3 = qkv.shape
-        x = qkv.contiguous().view(B, N, 3, heads, HEAD_DIM)
+        x = qkv.contiguous()
+        if x.data_ptr() % 16:   # a contiguous view at an odd storage offset: the kernels need 16 bytes
+            x = x.clone()
+        x = x.view(B, N, 3, heads, HEAD_DIM)
         q, k, v = x[:, :, 0], x[:, :, 1], x[:, :, 2]
         drop = (*_dropmask(B, heads, N, p, qkv.device), float(p)) if p > 0.0 else None
         out, lse = _fwd(q, k, v, scale, drop)
@@ -162,7 +176,7 @@ def sdpa(q, k, v, scale=None):
     """F.scaled_dot_product_attention(q, k, v) (no mask / dropout) for (B, H, N, d) inputs: the
     HIP kernels when supported, else PyTorch."""
     B, H, N, d = q.shape
-    if not supported(q, N, d) or k.shape != q.shape or v.shape != q.shape:
+    if not supported(q, N, d, scale, B * H) or k.shape != q.shape or v.shape != q.shape:
         return F.scaled_dot_product_attention(q, k, v, scale=scale)
     o = attention_bnhd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), scale)
     return o.transpose(1, 2)
@@ -177,7 +191,8 @@ def hf_attention_forward(module, query, key, value, attention_mask, dropout=0.0,
     B, H, N, d = query.shape
     p = float(dropout) if module.training else 0.0
     if (attention_mask is not None or kwargs.get("output_attentions") or not 0.0 <= p < 1.0
-            or key.shape != query.shape or value.shape != query.shape or not supported(query, N, d)
+            or key.shape != query.shape or value.shape != query.shape
+            or not supported(query, N, d, scaling, B * H)
             or getattr(module, "is_causal", False)):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)

@@ -421,7 +421,15 @@ __global__ __launch_bounds__(256) void attn_dropmask_kernel(int N, int nkt, unsi
   }
 }
 
-bool attn_ok(int B, int H, int N, int D) { return B > 0 && H > 0 && N > 0 && N <= MAX_KT * 32 && D == HD; }
+// Shape, scale and grid checks of every entry point: blockIdx.y is the (sample, head) index, and the
+// forward takes the row max of the unscaled scores (a scale <= 0 would turn it into the row min).
+bool attn_ok(int B, int H, int N, int D, float scale) {
+  return B > 0 && H > 0 && N > 0 && N <= MAX_KT * 32 && D == HD && (long long)B * H <= 65535 &&
+         scale > 0.f && scale < INFINITY;  // (false for NaN)
+}
+// One tensor of the ABI: non-null, 16-byte aligned, strides in whole bf16x8 vectors (the kernels read
+// and write rows with 16- and 8-byte accesses at base + b sB + n sN + 64 h + 8 c).
+bool row_ok(const void* p, long long sB, long long sN) { return p && !((uintptr_t)p & 15) && !(sB % 8) && !(sN % 8); }
 
 }  // namespace
 
@@ -441,7 +449,9 @@ int triad_attn_fwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            long long k_sN, const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D,
                            float scale, const unsigned* wq, float p, void* out, long long out_sB, long long out_sN,
                            float* lse, hipStream_t stream) {
-  if (!attn_ok(B, H, N, D) || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (!attn_ok(B, H, N, D, scale) || !(p >= 0.f && p < 1.f) || !lse) return TRIAD_EINVAL;
+  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(out, out_sB, out_sN))
+    return TRIAD_EINVAL;
   AttnArgs a = {};
   a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
   a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
@@ -471,7 +481,11 @@ int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            const unsigned* wk, float p, void* dq, long long dq_sB, long long dq_sN, void* dk,
                            long long dk_sB, long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta,
                            hipStream_t stream) {
-  if (!attn_ok(B, H, N, D) || p < 0.f || p >= 1.f || (!wq != !wk)) return TRIAD_EINVAL;
+  if (!attn_ok(B, H, N, D, scale) || !(p >= 0.f && p < 1.f) || (!wq != !wk) || !lse || !delta) return TRIAD_EINVAL;
+  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(o, o_sB, o_sN) ||
+      !row_ok(dout, do_sB, do_sN) || !row_ok(dq, dq_sB, dq_sN) || !row_ok(dk, dk_sB, dk_sN) ||
+      !row_ok(dv, dv_sB, dv_sN))
+    return TRIAD_EINVAL;
   AttnArgs a = {};
   a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
   a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
