@@ -460,6 +460,35 @@ int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            long long dk_sB, long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta,
                            hipStream_t stream);
 
+/* The same attention for longer sequences, 321 <= N <= 2048 (DINOv2-L/14 at 518 px: 1374 tokens;
+ * HuBERT-large on 10 s of audio: 499): K / V (forward, dq) or Q / dO (dk, dv) are streamed through LDS
+ * in chunks of 64 rows, the forward keeps an online softmax per query (running max and sum, O and
+ * the sum rescaled by exp2(mo_old - mo_new) per chunk). Tensors, scale, lse, delta and the meaning of
+ * the outputs are those of triad_attn_fwd_dropout / triad_attn_bwd_dropout. No atomics: results are
+ * bit-identical from run to run. N <= 320 is rejected here: the kernels above are faster there.
+ * Dropout keep bits: the same hash of element (bh N + q) N + key, stored by triad_attn_long_dropmask
+ * in two layouts of wpr = 2 ceil(N/64) words per row (rows padded to whole 64-key chunks):
+ * wq[(bh N + q) wpr + kt] (bit j = key 32 kt + j) and wk[(bh N + key) wpr + qt] (bit j = query 32 qt + j),
+ * bits of keys / queries >= N zero; B*H*N*wpr u32 each. NULL masks = no dropout (p is then ignored
+ * but still checked).
+ * TRIAD_EINVAL before any launch for: N <= 320 or N > 2048; D != 64; B or H <= 0, B*H > 65535; a scale
+ * that is not finite or <= 0; p outside [0, 1); a null or not 16-byte aligned q, k, v, out, o, dout,
+ * dq, dk or dv; an sB or sN that is not a multiple of 8 elements; a null lse, or a null delta in
+ * the backward; one of wq, wk null and the other not (backward), either null (dropmask); a mask
+ * pointer that is not 8-byte aligned (the kernels read two words at a time). */
+int triad_attn_long_dropmask(int B, int H, int N, float p, unsigned seed, unsigned* wq, unsigned* wk,
+                             hipStream_t stream);
+int triad_attn_long_fwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
+                        const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D, float scale,
+                        const unsigned* wq, float p, void* out, long long out_sB, long long out_sN, float* lse,
+                        hipStream_t stream);
+int triad_attn_long_bwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
+                        const void* v, long long v_sB, long long v_sN, const void* o, long long o_sB, long long o_sN,
+                        const void* dout, long long do_sB, long long do_sN, const float* lse, int B, int H, int N,
+                        int D, float scale, const unsigned* wq, const unsigned* wk, float p, void* dq, long long dq_sB,
+                        long long dq_sN, void* dk, long long dk_sB, long long dk_sN, void* dv, long long dv_sB,
+                        long long dv_sN, float* delta, hipStream_t stream);
+
 /* LoRA skinny products (model.py:223-266, peft LoRA r = 8 on the ViT's attn.qkv / attn.proj):
  * triad_rows_nt: out[m][j] = sum_k X[m][k] * W[j][k], X [M][ldx] bf16, W [J][K] bf16, J <= 16,
  *                K % 32 == 0, out [M][J] bf16 (t = x A^T).

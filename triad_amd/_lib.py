@@ -106,6 +106,11 @@ SIGNATURES = {
     "triad_attn_fwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, i64, i64, vp, vp],
     "triad_attn_bwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32,
                        i32, f32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp],
+    "triad_attn_long_dropmask": [i32, i32, i32, f32, u32, vp, vp, vp],
+    "triad_attn_long_fwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, f32, vp, i64, i64,
+                            vp, vp],
+    "triad_attn_long_bwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32,
+                            i32, f32, vp, vp, f32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp],
     "triad_dense_nparts": [i64],
     "triad_dense_rowmax": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "triad_nonneg_fwd": [vp, i64, f32, vp, vp],
@@ -132,7 +137,8 @@ BACKBONE_ENTRY_POINTS = frozenset({
     "triad_posconv", "triad_posconv_dw", "triad_gemm_bf16_splitk", "triad_rows_nt", "triad_lora_update",
     "triad_dropaddln_fwd", "triad_dropaddln_bwd", "triad_gelu_table", "triad_geludrop_fwd", "triad_geludrop_bwd",
     "triad_dropout_keep", "triad_addln_fwd", "triad_addln_bwd", "triad_lora_tn", "triad_attn_dropmask",
-    "triad_attn_fwd_dropout", "triad_attn_bwd_dropout", "triad_attn_fwd", "triad_attn_bwd"})
+    "triad_attn_fwd_dropout", "triad_attn_bwd_dropout", "triad_attn_fwd", "triad_attn_bwd",
+    "triad_attn_long_dropmask", "triad_attn_long_fwd", "triad_attn_long_bwd"})
 
 
 def hot_path_entry_points():

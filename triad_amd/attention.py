@@ -6,8 +6,14 @@ frames, 32 text tokens -- with head dim 64. PyTorch-ROCm's flash-attention kerne
 long sequences; here each (sample, head) sequence sits in LDS and a wave keeps a whole 32-row
 tile of scores in registers (exact softmax, no online rescaling). Used for mask-free attention
 with N <= 320 and head dim 64 in bf16, with or without dropout on the attention probabilities
-(keep bits from the common.h counter hash, stored as bit words for the backward); anything
-else goes to F.scaled_dot_product_attention.
+(keep bits from the common.h counter hash, stored as bit words for the backward).
+
+Longer sequences, 321 .. 2048 tokens (configuration c5: 1374 visual tokens of DINOv2-L/14 at
+518 px, 499 audio frames of HuBERT-large on 10 s), take the streaming kernels of
+csrc/attention_long.hip: K / V (or Q / dO) pass through LDS in chunks of 64 rows and the forward
+keeps an online softmax per query; same tensors, same dropout bits, words padded to whole chunks.
+Which token counts are routed there is LONG_ROUTE. Anything else -- masks, causal attention, head
+dim != 64, fp32, N > 2048 -- goes to F.scaled_dot_product_attention.
 """
 from __future__ import annotations
 
@@ -20,7 +26,11 @@ from ._lib import call, ptr, stream_ptr
 
 HEAD_DIM = 64
 MAX_TOKENS = 320
+MAX_TOKENS_LONG = 2048
 MAX_SEQUENCES = 65535   # B * H: one grid row per (sample, head)
+# token counts the wrappers send to the streaming kernels (inclusive). The entry points accept all of
+# 321 .. 2048; narrow this only where a measurement shows PyTorch's kernels ahead
+LONG_ROUTE = (321, 2048)
 
 
 def supported(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int = 1) -> bool:
@@ -30,6 +40,16 @@ def supported(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int
     if scale is not None and not (math.isfinite(scale) and scale > 0.0):
         return False
     return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and 0 < n <= MAX_TOKENS
+            and 0 < sequences <= MAX_SEQUENCES)
+
+
+def supported_long(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int = 1) -> bool:
+    """What the wrappers send to the streaming kernels (triad_attn_long_*): as `supported`, with
+    LONG_ROUTE[0] <= n <= LONG_ROUTE[1] tokens (inside the entry points' 321 .. 2048)."""
+    if scale is not None and not (math.isfinite(scale) and scale > 0.0):
+        return False
+    lo, hi = max(LONG_ROUTE[0], MAX_TOKENS + 1), min(LONG_ROUTE[1], MAX_TOKENS_LONG)
+    return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and lo <= n <= hi
             and 0 < sequences <= MAX_SEQUENCES)
 
 
@@ -57,6 +77,24 @@ def _dropmask(B, H, N, p, device):
     return wq, wk
 
 
+def _dropmask_long(B, H, N, p, device):
+    """The same keep bits for the streaming kernels: 2 ceil(N / 64) words per row (triad_attn_long_dropmask)."""
+    wpr = 2 * ((N + 63) // 64)
+    wq = torch.empty(B * H * N * wpr, dtype=torch.int32, device=device)
+    wk = torch.empty_like(wq)
+    call("triad_attn_long_dropmask", B, H, N, float(p), _SEEDS(), ptr(wq), ptr(wk), stream_ptr(device))
+    return wq, wk
+
+
+def _is_long(N):
+    """Which pair of kernels _Attention / _AttentionQKV run: the streaming ones past MAX_TOKENS."""
+    return N > MAX_TOKENS
+
+
+def _draw_mask(B, H, N, p, device):
+    return (_dropmask_long if _is_long(N) else _dropmask)(B, H, N, p, device)
+
+
 def _fwd(q, k, v, scale, drop=None):
     B, N, H, D = q.shape
     out = torch.empty(B, N, H, D, dtype=torch.bfloat16, device=q.device)
@@ -81,6 +119,31 @@ def _bwd(q, k, v, out, lse, dout, scale, drop=None):
     return g
 
 
+def _fwd_long(q, k, v, scale, drop=None):
+    """_fwd on the streaming kernels (321 <= N <= 2048)."""
+    B, N, H, D = q.shape
+    out = torch.empty(B, N, H, D, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
+    wq, p = (drop[0], drop[2]) if drop is not None else (None, 0.0)
+    call("triad_attn_long_fwd", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), B, H, N, D, float(scale),
+         ptr(wq), float(p), ptr(out), *_rows(out), ptr(lse), stream_ptr(q.device))
+    return out, lse
+
+
+def _bwd_long(q, k, v, out, lse, dout, scale, drop=None):
+    """_bwd on the streaming kernels: the same (B, N, 3, H, 64) gradient buffer."""
+    B, N, H, D = q.shape
+    do = _as_bnhd(dout.to(torch.bfloat16))
+    g = torch.empty(B, N, 3, H, D, dtype=torch.bfloat16, device=q.device)
+    dq, dk, dv = g[:, :, 0], g[:, :, 1], g[:, :, 2]
+    delta = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
+    wq, wk, p = drop if drop is not None else (None, None, 0.0)
+    call("triad_attn_long_bwd", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), ptr(out), *_rows(out),
+         ptr(do), *_rows(do), ptr(lse), B, H, N, D, float(scale), ptr(wq), ptr(wk), float(p), ptr(dq), *_rows(dq),
+         ptr(dk), *_rows(dk), ptr(dv), *_rows(dv), ptr(delta), stream_ptr(q.device))
+    return g
+
+
 def _SEEDS():
     """Per-call 32-bit dropout seed drawn from torch's default CPU generator (no device sync):
     torch.manual_seed reproduces the masks, as it does for torch's own dropout kernels."""
@@ -89,7 +152,8 @@ def _SEEDS():
 
 class _Attention(torch.autograd.Function):
     """q, k, v: (B, N, H, 64) bf16 views (head dim contiguous, heads adjacent) -> O (B, N, H, 64);
-    dropout p > 0 drops attention probabilities (keep bits drawn per call, kept for the backward)."""
+    N <= 320 on the whole-sequence kernels, longer on the streaming ones; dropout p > 0 drops
+    attention probabilities (keep bits drawn per call, kept for the backward)."""
 
     @staticmethod
     def forward(ctx, q, k, v, scale, p=0.0):
@@ -97,8 +161,8 @@ class _Attention(torch.autograd.Function):
         drop = None
         if p > 0.0:
             B, N, H, _ = q.shape
-            drop = (*_dropmask(B, H, N, p, q.device), float(p))
-        out, lse = _fwd(q, k, v, scale, drop)
+            drop = (*_draw_mask(B, H, N, p, q.device), float(p))
+        out, lse = (_fwd_long if _is_long(q.shape[1]) else _fwd)(q, k, v, scale, drop)
         ctx.save_for_backward(q, k, v, out, lse, *(drop[:2] if drop else ()))
         ctx.scale = float(scale)
         ctx.p = float(p)
@@ -109,7 +173,7 @@ class _Attention(torch.autograd.Function):
         saved = ctx.saved_tensors
         q, k, v, out, lse = saved[:5]
         drop = (saved[5], saved[6], ctx.p) if ctx.p > 0.0 else None
-        g = _bwd(q, k, v, out, lse, dout, ctx.scale, drop)
+        g = (_bwd_long if _is_long(q.shape[1]) else _bwd)(q, k, v, out, lse, dout, ctx.scale, drop)
         return g[:, :, 0], g[:, :, 1], g[:, :, 2], None, None
 
 
@@ -126,8 +190,8 @@ class _AttentionQKV(torch.autograd.Function):
             x = x.clone()
         x = x.view(B, N, 3, heads, HEAD_DIM)
         q, k, v = x[:, :, 0], x[:, :, 1], x[:, :, 2]
-        drop = (*_dropmask(B, heads, N, p, qkv.device), float(p)) if p > 0.0 else None
-        out, lse = _fwd(q, k, v, scale, drop)
+        drop = (*_draw_mask(B, heads, N, p, qkv.device), float(p)) if p > 0.0 else None
+        out, lse = (_fwd_long if _is_long(N) else _fwd)(q, k, v, scale, drop)
         ctx.save_for_backward(x, out, lse, *(drop[:2] if drop else ()))
         ctx.scale = float(scale)
         ctx.p = float(p)
@@ -139,7 +203,8 @@ class _AttentionQKV(torch.autograd.Function):
         x, out, lse = saved[:3]
         drop = (saved[3], saved[4], ctx.p) if ctx.p > 0.0 else None
         B, N = x.shape[0], x.shape[1]
-        g = _bwd(x[:, :, 0], x[:, :, 1], x[:, :, 2], out, lse, dout.view(out.shape), ctx.scale, drop)
+        g = (_bwd_long if _is_long(N) else _bwd)(x[:, :, 0], x[:, :, 1], x[:, :, 2], out, lse, dout.view(out.shape),
+                                                 ctx.scale, drop)
         return g.view(B, N, -1), None, None, None
 
 
@@ -174,9 +239,10 @@ def dropout_keep_dense(B, H, N, p, seed, device):
 
 def sdpa(q, k, v, scale=None):
     """F.scaled_dot_product_attention(q, k, v) (no mask / dropout) for (B, H, N, d) inputs: the
-    HIP kernels when supported, else PyTorch."""
+    HIP kernels when supported (<= 320 tokens, or LONG_ROUTE on the streaming kernels), else PyTorch."""
     B, H, N, d = q.shape
-    if not supported(q, N, d, scale, B * H) or k.shape != q.shape or v.shape != q.shape:
+    hip = supported(q, N, d, scale, B * H) or supported_long(q, N, d, scale, B * H)
+    if not hip or k.shape != q.shape or v.shape != q.shape:
         return F.scaled_dot_product_attention(q, k, v, scale=scale)
     o = attention_bnhd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), scale)
     return o.transpose(1, 2)
@@ -185,14 +251,15 @@ def sdpa(q, k, v, scale=None):
 def hf_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, is_causal=None,
                          **kwargs):
     """transformers attention-interface function ("triad"): the HIP kernels for unmasked attention
-    over <= 320 tokens (attention dropout included), else the stock sdpa implementation.
+    over <= 320 tokens, or LONG_ROUTE tokens on the streaming kernels (attention dropout included),
+    else the stock sdpa implementation.
     Returns (B, N, H, d) as the interface requires."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
     B, H, N, d = query.shape
     p = float(dropout) if module.training else 0.0
     if (attention_mask is not None or kwargs.get("output_attentions") or not 0.0 <= p < 1.0
             or key.shape != query.shape or value.shape != query.shape
-            or not supported(query, N, d, scaling, B * H)
+            or not (supported(query, N, d, scaling, B * H) or supported_long(query, N, d, scaling, B * H))
             or getattr(module, "is_causal", False)):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)

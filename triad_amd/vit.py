@@ -9,7 +9,8 @@ blocks.N.{norm1,attn.qkv,attn.proj,ls1,norm2,mlp.fc1,mlp.fc2,ls2}, norm), so a h
 state_dict loads into it, and implements LoRA directly (`lora_A` / `lora_B`
 parameters, names containing "lora" as train.py:256-258 expects).
 Backbone numerics are "parity unpinned": no pretrained weights exist offline.
-Attention uses torch's fused scaled_dot_product_attention (ROCm flash kernels).
+Attention runs on triad_amd.attention's HIP kernels up to 2048 tokens (head dim 64, bf16);
+otherwise on torch's fused scaled_dot_product_attention.
 """
 from __future__ import annotations
 
@@ -138,7 +139,9 @@ class Attention(nn.Module):
     def forward(self, x):
         B, N, C = x.shape
         qkv = self.qkv(x)
-        if attention.supported(qkv, N, C // self.heads):  # HIP kernels (triad_amd.attention)
+        d = C // self.heads
+        if attention.supported(qkv, N, d) or \
+                attention.supported_long(qkv, N, d, None, B * self.heads):  # HIP kernels (triad_amd.attention)
             return self.proj(attention.attention_qkv(qkv, self.heads))
         qkv = qkv.reshape(B, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2])
