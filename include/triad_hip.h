@@ -383,7 +383,10 @@ int triad_l2norm_rows_f32(const float* x, int rows, int D, float eps, float* y, 
  * fwd: y = bf16(gelu((x - mean[b][c]) * rstd[b][c] * gamma[c] + beta[c])), statistics over t < T
  *      in fp32/fp64, mean / rstd (B*C floats) saved for the backward.
  * bwd: dx (bf16) and dgamma / dbeta (C floats, overwritten) from dy (bf16).
- * ws: triad_chgn_workspace_bytes(B, T, C) bytes of scratch. */
+ * ws: triad_chgn_workspace_bytes(B, T, C) bytes of scratch.
+ * Every pointer is required (NULL -> TRIAD_EINVAL). x, y, dy, dx and ws 16-byte aligned (16-byte vector
+ * loads / stores; ws holds float2 / double2 records); gamma, beta, mean, rstd, dgamma, dbeta 4-byte
+ * aligned; B <= 65535 (a grid dimension), Tp >= T. All checked before any launch. */
 long long triad_chgn_workspace_bytes(int B, int T, int C);
 int triad_chgn_gelu_fwd(const void* x, int B, int T, int Tp, int C, const float* gamma, const float* beta,
                         float eps, float* mean, float* rstd, void* ws, void* y, hipStream_t stream);
@@ -394,13 +397,19 @@ int triad_chgn_gelu_bwd(const void* x, const void* dy, int B, int T, int Tp, int
 /* HuBERT conv layer 0 (1 -> C, kernel 10, stride 5, no bias) + GroupNorm(C groups) + GELU forward with
  * conv0 recomputed from the bf16 waveform wave[b][Lp] (Lp >= 5 (Tp - 1) + 10) in both passes; writes the
  * padded frame buffers out = bf16(gelu(gn(y0))) and y0out = y0 (frames T .. Tp-1 zero) and mean / rstd;
- * the backward is triad_chgn_gelu_bwd over y0out. ws: triad_chgn_workspace_bytes(B, T, C) bytes. */
+ * the backward is triad_chgn_gelu_bwd over y0out. ws: triad_chgn_workspace_bytes(B, T, C) bytes.
+ * Samples past 5 (T - 1) + 9 of a row are never read (Lp only has to make them exist). Every pointer is
+ * required; wave 2-byte aligned, w0 (C x 10 bf16, read as 16-byte vectors), out, y0out and ws 16-byte
+ * aligned, gamma, beta, mean, rstd 4-byte aligned; B <= 65535. Else TRIAD_EINVAL before any launch. */
 int triad_c0gn_fwd(const void* wave, long long Lp, const void* w0, int B, int T, int Tp, int C, const float* gamma,
                    const float* beta, float eps, float* mean, float* rstd, void* ws, void* out, void* y0out,
                    hipStream_t stream);
 
 /* conv0's weight gradient dw0[c][j] (fp32) = sum_{b, t < T} dy0[b*Tp + t][c] * wave[b][5t + j] (bf16 inputs);
- * ws: triad_conv0_dw_workspace_bytes(B, T, C) bytes. */
+ * ws: triad_conv0_dw_workspace_bytes(B, T, C) bytes (per-block fp32 slabs, all written). Lp >= 5 (T - 1) + 10;
+ * dy0's frames T .. Tp-1 and the samples past 5 (T - 1) + 9 are never read. Every pointer is required; wave
+ * 2-byte aligned, dy0 and ws 16-byte aligned, dw0 4-byte aligned; B <= 65535. Else TRIAD_EINVAL before any
+ * launch. */
 long long triad_conv0_dw_workspace_bytes(int B, int T, int C);
 int triad_conv0_dw(const void* wave, long long Lp, const void* dy0, int B, int T, int Tp, int C, void* ws, float* dw0,
                    hipStream_t stream);
@@ -410,14 +419,18 @@ int triad_conv0_dw(const void* wave, long long Lp, const void* dy0, int B, int T
  * y[b][t][g*CG+n] = bias + sum_{j<128, c<CG} x[b][t+j-pad][g*CG+c] * wt[g][n][j*CG+c], t < T,
  * x zero outside [0, T); CG = C/groups in {48, 64}; bias f32 (may be NULL).
  * Forward: wt[g][n][j*CG+c] = W[g*CG+n][c][j], pad = 64. Input gradient: x = dy,
- * wt[g][c][j*CG+n] = W[g*CG+n][c][127-j], pad = 63. */
+ * wt[g][c][j*CG+n] = W[g*CG+n][c][127-j], pad = 63. 0 <= pad < 128.
+ * x, wt and y are required and 16-byte aligned (16-byte vector loads and LDS-DMA); bias, where given, 4-byte
+ * aligned; B <= 65535 and ceil(T / 208) <= 65535 (grid dimensions). Else TRIAD_EINVAL before any launch. */
 int triad_posconv(const void* x, const void* wt, const float* bias, void* y, int B, int T, int C, int groups,
                   int pad, hipStream_t stream);
 
 /* Weight gradient of the same conv (C / groups == 48): fp32 partials part[s][g][j][n][c] over
  * `splits` contiguous sample ranges, dW[g*48 + n][c][j] = sum_s part[...]; part holds
  * triad_posconv_dw_part_bytes(C, groups, splits) bytes. Replaces aten's grouped-conv weight
- * gradient (transformers HubertPositionalConvEmbedding backward). */
+ * gradient (transformers HubertPositionalConvEmbedding backward). Every slab is written, a split
+ * without samples (splits > B) as zeros. x, dy and part are required; x and dy 16-byte aligned, part
+ * 4-byte aligned; 1 <= splits <= 65535. Else TRIAD_EINVAL before any launch. */
 long long triad_posconv_dw_part_bytes(int C, int groups, int splits);
 int triad_posconv_dw(const void* x, const void* dy, int B, int T, int C, int groups, int pad, int splits, float* part,
                      hipStream_t stream);

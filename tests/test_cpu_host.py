@@ -258,6 +258,84 @@ def test_vit_row_entry_points_reject_bad_arguments():
         assert f(M=0) == 1001 and f(M=-4) == 1001, f.__name__
 
 
+def test_frontend_entry_points_reject_bad_arguments():
+    """The HuBERT front-end entry points (csrc/frontend.hip, csrc/posconv.hip) validate before any
+    launch (no GPU needed) -> TRIAD_EINVAL (1001): NULL required pointers, bf16 tensors / w0 / wt / ws
+    off 16 bytes, fp32 vectors off 4 bytes, the waveform off 2 bytes, B and the time-block count past
+    the grid limits, and every older shape rule. One assertion per rule; each helper's defaults are a
+    valid call the others differ from in one argument."""
+    from triad_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libtriad_hip.so is not built")
+    lib = _lib.load()
+    fake = 4096  # 16-byte aligned, never dereferenced: validation fails first
+
+    def fwd(B=2, T=100, Tp=100, C=512, **p):
+        a = dict(x=fake, gamma=fake, beta=fake, mean=fake, rstd=fake, ws=fake, y=fake)
+        a.update(p)
+        return lib.triad_chgn_gelu_fwd(a["x"], B, T, Tp, C, a["gamma"], a["beta"], 1e-5, a["mean"], a["rstd"],
+                                       a["ws"], a["y"], None)
+
+    def bwd(B=2, T=100, Tp=100, C=512, **p):
+        a = dict(x=fake, dy=fake, gamma=fake, beta=fake, mean=fake, rstd=fake, ws=fake, dx=fake, dgamma=fake,
+                 dbeta=fake)
+        a.update(p)
+        return lib.triad_chgn_gelu_bwd(a["x"], a["dy"], B, T, Tp, C, a["gamma"], a["beta"], a["mean"], a["rstd"],
+                                       a["ws"], a["dx"], a["dgamma"], a["dbeta"], None)
+
+    def c0gn(B=2, T=100, Tp=100, C=512, Lp=505, **p):
+        a = dict(wave=fake, w0=fake, gamma=fake, beta=fake, mean=fake, rstd=fake, ws=fake, out=fake, y0out=fake)
+        a.update(p)
+        return lib.triad_c0gn_fwd(a["wave"], Lp, a["w0"], B, T, Tp, C, a["gamma"], a["beta"], 1e-5, a["mean"],
+                                  a["rstd"], a["ws"], a["out"], a["y0out"], None)
+
+    def c0dw(B=2, T=100, Tp=100, C=512, Lp=505, **p):
+        a = dict(wave=fake, dy0=fake, ws=fake, dw0=fake)
+        a.update(p)
+        return lib.triad_conv0_dw(a["wave"], Lp, a["dy0"], B, T, Tp, C, a["ws"], a["dw0"], None)
+
+    def pos(B=2, T=100, C=768, groups=16, pad=64, **p):
+        a = dict(x=fake, wt=fake, bias=fake, y=fake)
+        a.update(p)
+        return lib.triad_posconv(a["x"], a["wt"], a["bias"], a["y"], B, T, C, groups, pad, None)
+
+    def posdw(B=2, T=100, C=768, groups=16, pad=64, splits=2, **p):
+        a = dict(x=fake, dy=fake, part=fake)
+        a.update(p)
+        return lib.triad_posconv_dw(a["x"], a["dy"], B, T, C, groups, pad, splits, a["part"], None)
+
+    vec16 = {fwd: ("x", "y", "ws"), bwd: ("x", "dy", "dx", "ws"), c0gn: ("w0", "out", "y0out", "ws"),
+             c0dw: ("dy0", "ws"), pos: ("x", "wt", "y"), posdw: ("x", "dy")}
+    f32s = {fwd: ("gamma", "beta", "mean", "rstd"), bwd: ("gamma", "beta", "mean", "rstd", "dgamma", "dbeta"),
+            c0gn: ("gamma", "beta", "mean", "rstd"), c0dw: ("dw0",), pos: (), posdw: ("part",)}
+    for f, names in vec16.items():
+        for n in names:
+            assert f(**{n: None}) == 1001, (f.__name__, n, "NULL")
+            assert f(**{n: fake + 2}) == 1001 and f(**{n: fake + 8}) == 1001, (f.__name__, n, "16-byte alignment")
+    for f, names in f32s.items():
+        for n in names:
+            assert f(**{n: None}) == 1001, (f.__name__, n, "NULL")
+            assert f(**{n: fake + 2}) == 1001, (f.__name__, n, "4-byte alignment")
+    for f in (c0gn, c0dw):
+        assert f(wave=None) == 1001 and f(wave=fake + 1) == 1001, f.__name__       # waveform: NULL, 2-byte alignment
+    assert pos(bias=fake + 2) == 1001                                              # bias optional, but aligned
+    for f in (fwd, bwd, c0gn, c0dw, pos):
+        assert f(B=65536) == 1001 and f(B=0) == 1001, f.__name__                   # gridDim.y
+    assert pos(T=208 * 65535 + 1) == 1001                                          # gridDim.z
+    # the older rules
+    for f in (fwd, bwd, c0gn, c0dw):
+        assert f(T=0) == 1001 and f(Tp=99) == 1001, f.__name__                     # T > 0, Tp >= T
+        assert f(C=100) == 1001 and f(C=24) == 1001 and f(C=0) == 1001, f.__name__  # C % 8, 256 % (C / 8)
+    assert c0gn(Tp=101, Lp=509) == 1001 and c0gn(Lp=504) == 1001                   # Lp >= 5 (Tp - 1) + 10
+    assert c0dw(Lp=504) == 1001                                                    # Lp >= 5 (T - 1) + 10
+    for f in (pos, posdw):
+        assert f(T=0) == 1001 and f(groups=0) == 1001 and f(C=770) == 1001, f.__name__
+        assert f(pad=-1) == 1001 and f(pad=128) == 1001, f.__name__
+    assert pos(C=512, groups=16) == 1001                                           # CG in {48, 64}
+    assert posdw(C=1024, groups=16) == 1001                                        # CG == 48 only
+    assert posdw(B=0) == 1001 and posdw(splits=0) == 1001 and posdw(splits=65536) == 1001
+
+
 def test_packed_tile_gemm_and_patch_reject_bad_arguments():
     """The direct-B GEMM entry points, the dS patch and the loss head validate their shapes before
     launching anything (no GPU needed) -> TRIAD_EINVAL (1001)."""

@@ -1,7 +1,9 @@
 """GPU parity of the backbone front-ends (triad_amd.frontend): the fused channels-last
 GroupNorm(C groups) + GELU HIP kernels against torch fp32 (values, dx, dgamma, dbeta), and the
 whole HuBERT conv feature encoder in GEMM form against the transformers modules it replaces,
-both under bf16 autocast on the device."""
+both under bf16 autocast on the device. These are whole-tensor relative-norm comparisons with
+another bf16 / fp32 path; the per-element checks of the same kernels against fp64 references, through
+the C ABI, are in tests/test_frontend_conformance_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -379,9 +379,15 @@ __global__ __launch_bounds__(NT) void c0dw_kernel(const bf16* __restrict__ wave,
   }
 }
 
+// B is gridDim.y of every launch here (limit 65535)
 bool shape_ok(int B, int T, int C) {
-  return B > 0 && T > 0 && C > 0 && C % 8 == 0 && NT % (C / 8) == 0;
+  return B > 0 && B <= 65535 && T > 0 && C > 0 && C % 8 == 0 && NT % (C / 8) == 0;
 }
+
+// non-NULL and aligned to `a` bytes (a power of two): 16 for what load8 / store8 / bf16x8 touch (bf16
+// frame buffers, w0) and for the workspace (float2 / double2 records), 4 for fp32 vectors, 2 for the
+// waveform (scalar bf16 loads)
+bool ptr_ok(const void* p, uintptr_t a) { return p && !((uintptr_t)p & (a - 1)); }
 
 }  // namespace
 
@@ -396,6 +402,9 @@ long long triad_chgn_workspace_bytes(int B, int T, int C) {
 int triad_chgn_gelu_fwd(const void* x, int B, int T, int Tp, int C, const float* gamma, const float* beta,
                         float eps, float* mean, float* rstd, void* ws, void* y, hipStream_t stream) {
   if (!shape_ok(B, T, C) || Tp < T) return TRIAD_EINVAL;
+  if (!ptr_ok(x, 16) || !ptr_ok(y, 16) || !ptr_ok(ws, 16) || !ptr_ok(gamma, 4) || !ptr_ok(beta, 4) ||
+      !ptr_ok(mean, 4) || !ptr_ok(rstd, 4))
+    return TRIAD_EINVAL;
   const int nchunk = (T + CHUNK - 1) / CHUNK;
   float2* part = (float2*)ws;
   hipLaunchKernelGGL(chgn_sums_kernel<0>, dim3(nchunk, B), dim3(NT), 0, stream, (const bf16*)x, nullptr, T, Tp, C,
@@ -412,6 +421,9 @@ int triad_chgn_gelu_bwd(const void* x, const void* dy, int B, int T, int Tp, int
                         const float* beta, const float* mean, const float* rstd, void* ws, void* dx, float* dgamma,
                         float* dbeta, hipStream_t stream) {
   if (!shape_ok(B, T, C) || Tp < T) return TRIAD_EINVAL;
+  if (!ptr_ok(x, 16) || !ptr_ok(dy, 16) || !ptr_ok(dx, 16) || !ptr_ok(ws, 16) || !ptr_ok(gamma, 4) ||
+      !ptr_ok(beta, 4) || !ptr_ok(mean, 4) || !ptr_ok(rstd, 4) || !ptr_ok(dgamma, 4) || !ptr_ok(dbeta, 4))
+    return TRIAD_EINVAL;
   const int nchunk = (T + CHUNK - 1) / CHUNK;
   float2* part = (float2*)ws;
   float2* coef = part + (size_t)B * nchunk * C;
@@ -435,6 +447,9 @@ int triad_c0gn_fwd(const void* wave, long long Lp, const void* w0, int B, int T,
                    const float* beta, float eps, float* mean, float* rstd, void* ws, void* out, void* y0out,
                    hipStream_t stream) {
   if (!shape_ok(B, T, C) || Tp < T || Lp < (long long)C0_S * (Tp - 1) + C0_K) return TRIAD_EINVAL;
+  if (!ptr_ok(wave, 2) || !ptr_ok(w0, 16) || !ptr_ok(out, 16) || !ptr_ok(y0out, 16) || !ptr_ok(ws, 16) ||
+      !ptr_ok(gamma, 4) || !ptr_ok(beta, 4) || !ptr_ok(mean, 4) || !ptr_ok(rstd, 4))
+    return TRIAD_EINVAL;
   const int nchunk = (T + CHUNK - 1) / CHUNK;
   float2* part = (float2*)ws;
   hipLaunchKernelGGL(c0gn_kernel<0>, dim3(nchunk, B), dim3(NT), 0, stream, (const bf16*)wave, Lp, (const bf16*)w0, T,
@@ -455,6 +470,7 @@ long long triad_conv0_dw_workspace_bytes(int B, int T, int C) {
 int triad_conv0_dw(const void* wave, long long Lp, const void* dy0, int B, int T, int Tp, int C, void* ws, float* dw0,
                    hipStream_t stream) {
   if (!shape_ok(B, T, C) || Tp < T || Lp < (long long)C0_S * (T - 1) + C0_K) return TRIAD_EINVAL;
+  if (!ptr_ok(wave, 2) || !ptr_ok(dy0, 16) || !ptr_ok(ws, 16) || !ptr_ok(dw0, 4)) return TRIAD_EINVAL;
   const int nblk = (T + C0_DW_ROWS - 1) / C0_DW_ROWS;
   hipLaunchKernelGGL(c0dw_kernel, dim3(nblk, B), dim3(NT), 0, stream, (const bf16*)wave, Lp, (const bf16*)dy0, T, Tp,
                      C, (float*)ws);

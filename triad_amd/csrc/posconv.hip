@@ -218,6 +218,9 @@ __global__ __launch_bounds__(256, 2) void posconv_dw_kernel(const bf16* __restri
   }
 }
 
+// non-NULL and 16-byte aligned: the bf16 operands are read as bf16x8 vectors and by 16-byte LDS-DMA
+bool vec_ok(const void* p) { return p && !((uintptr_t)p & 15); }
+
 }  // namespace
 
 extern "C" {
@@ -225,6 +228,9 @@ extern "C" {
 int triad_posconv(const void* x, const void* wt, const float* bias, void* y, int B, int T, int C, int groups,
                   int pad, hipStream_t stream) {
   if (B <= 0 || T <= 0 || groups <= 0 || C % groups || pad < 0 || pad >= KT) return TRIAD_EINVAL;
+  // B is gridDim.y and the time-block count gridDim.z (limit 65535 each); bias stays optional
+  if (B > 65535 || ((long long)T + ROWS - 1) / ROWS > 65535) return TRIAD_EINVAL;
+  if (!vec_ok(x) || !vec_ok(wt) || !vec_ok(y) || ((uintptr_t)bias & 3)) return TRIAD_EINVAL;
   const int cg = C / groups;
   const dim3 grid(groups, B, (T + ROWS - 1) / ROWS);
   if (cg == 48)
@@ -250,6 +256,7 @@ int triad_posconv_dw(const void* x, const void* dy, int B, int T, int C, int gro
                      hipStream_t stream) {
   if (B <= 0 || T <= 0 || groups <= 0 || C % groups || pad < 0 || pad >= KT || splits <= 0 || splits > 65535)
     return TRIAD_EINVAL;
+  if (!vec_ok(x) || !vec_ok(dy) || !part || ((uintptr_t)part & 3)) return TRIAD_EINVAL;
   const int cg = C / groups, spb = (B + splits - 1) / splits;
   const dim3 grid(groups, KT / DW_TAPS, splits);
   if (cg != 48) return TRIAD_EINVAL;  // 4 taps x 9 tiles per wave fit the registers at CG = 48 only
