@@ -533,7 +533,12 @@ int triad_addln_bwd(const void* dln, int dln_f32, const float* dres, const float
  * triad_dropaddln_bwd: dres = LN'(dh + dhb) (either NULL), dy = bf16(bf16(dres) keep / (1-p)); part:
  *                      triad_dropaddln_bwd_blocks(M) x 2 x D fp32 dgamma / dbeta partials.
  * triad_geludrop_fwd / _bwd: v = bf16(bf16(gelu(u)) keep / (1-p)) over n bf16 (n % 8 == 0) and its gradient.
- * triad_dropout_keep: the keep bits (u8) for n elements (tests). */
+ * triad_dropout_keep: the keep bits (u8) for n elements (tests).
+ * Every entry point returns TRIAD_EINVAL before any launch unless: M > 0, D in {256, 512, 768, 1024}, n > 0
+ * (n % 8 == 0 for the GELU passes), 0 <= p < 1 (a NaN p is refused), eps finite and > 0; every pointer
+ * non-NULL except dh, dhb and table; fp32 row tensors and vectors read as f32x4 (res, h, dh, dres, w, b)
+ * and the table 16-byte aligned; bf16 row tensors (y, hb, dhb, dy) 8-byte aligned; u, v, dv, du 16-byte
+ * aligned; mean, rstd and part 4-byte aligned. An optional pointer that is given obeys its alignment. */
 int triad_dropaddln_fwd(const float* res, const void* y, const float* w, const float* b, float eps, int M, int D,
                         float p, unsigned seed, float* h, void* hb, float* mean, float* rstd, hipStream_t stream);
 int triad_dropaddln_bwd_blocks(int M);

@@ -336,6 +336,74 @@ def test_frontend_entry_points_reject_bad_arguments():
     assert posdw(B=0) == 1001 and posdw(splits=0) == 1001 and posdw(splits=65536) == 1001
 
 
+def test_postln_entry_points_reject_bad_arguments():
+    """The post-LN entry points (csrc/postln.hip) validate before any launch (no GPU needed) ->
+    TRIAD_EINVAL (1001): NULL required pointers (dh, dhb and the table stay optional), fp32 row tensors
+    / w / b / the table off 16 bytes, bf16 row tensors off 8 bytes, the GELU operands off 16 bytes,
+    mean / rstd / part off 4 bytes, eps not finite or <= 0, p NaN, and the older size rules. One
+    assertion per rule; each helper's defaults are a valid call the others differ from in one
+    argument."""
+    from triad_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libtriad_hip.so is not built")
+    lib = _lib.load()
+    fake = 4096  # 16-byte aligned, never dereferenced: validation fails first
+    nan, inf = float("nan"), float("inf")
+
+    def fwd(M=64, D=768, p=0.1, eps=1e-5, **a):
+        a = {**dict(res=fake, y=fake, w=fake, b=fake, h=fake, hb=fake, mean=fake, rstd=fake), **a}
+        return lib.triad_dropaddln_fwd(a["res"], a["y"], a["w"], a["b"], eps, M, D, p, 7, a["h"], a["hb"], a["mean"],
+                                       a["rstd"], None)
+
+    def bwd(M=64, D=768, p=0.1, **a):
+        a = {**dict(dh=fake, dhb=fake, res=fake, y=fake, mean=fake, rstd=fake, w=fake, dres=fake, dy=fake, part=fake),
+             **a}
+        return lib.triad_dropaddln_bwd(a["dh"], a["dhb"], a["res"], a["y"], a["mean"], a["rstd"], a["w"], M, D, p, 7,
+                                       a["dres"], a["dy"], a["part"], None)
+
+    def gfwd(n=4096, p=0.1, **a):
+        a = {**dict(u=fake, table=fake, v=fake), **a}
+        return lib.triad_geludrop_fwd(a["u"], n, p, 7, a["table"], a["v"], None)
+
+    def gbwd(n=4096, p=0.1, **a):
+        a = {**dict(u=fake, dv=fake, table=fake, du=fake), **a}
+        return lib.triad_geludrop_bwd(a["u"], a["dv"], n, p, 7, a["table"], a["du"], None)
+
+    def keep(n=4096, p=0.1, out=fake):
+        return lib.triad_dropout_keep(n, p, 7, out, None)
+
+    f32_16 = {fwd: ("res", "w", "b", "h"), bwd: ("res", "w", "dres"), gfwd: ("u", "v"), gbwd: ("u", "dv", "du")}
+    bf16_8 = {fwd: ("y", "hb"), bwd: ("y", "dy")}
+    f32_4 = {fwd: ("mean", "rstd"), bwd: ("mean", "rstd", "part")}
+    for f, names in f32_16.items():
+        for n in names:
+            assert f(**{n: None}) == 1001, (f.__name__, n, "NULL")
+            assert f(**{n: fake + 4}) == 1001 and f(**{n: fake + 8}) == 1001, (f.__name__, n, "16-byte alignment")
+    for f, names in bf16_8.items():
+        for n in names:
+            assert f(**{n: None}) == 1001, (f.__name__, n, "NULL")
+            assert f(**{n: fake + 2}) == 1001 and f(**{n: fake + 4}) == 1001, (f.__name__, n, "8-byte alignment")
+    for f, names in f32_4.items():
+        for n in names:
+            assert f(**{n: None}) == 1001, (f.__name__, n, "NULL")
+            assert f(**{n: fake + 2}) == 1001, (f.__name__, n, "4-byte alignment")
+    assert bwd(dh=fake + 8) == 1001 and bwd(dhb=fake + 4) == 1001              # optional, but aligned when given
+    assert gfwd(table=fake + 8) == 1001 and gbwd(table=fake + 8) == 1001
+    assert lib.triad_gelu_table(None, None) == 1001 and lib.triad_gelu_table(fake + 8, None) == 1001
+    assert keep(out=None) == 1001
+    for eps in (0.0, -1e-5, nan, inf):
+        assert fwd(eps=eps) == 1001, eps
+    for f in (fwd, bwd, gfwd, gbwd, keep):
+        assert f(p=nan) == 1001, f.__name__
+        assert f(p=-0.1) == 1001 and f(p=1.0) == 1001, f.__name__                # the older rules
+    for f in (fwd, bwd):
+        assert f(M=0) == 1001 and f(M=-4) == 1001, f.__name__
+        assert f(D=0) == 1001 and f(D=800) == 1001 and f(D=1280) == 1001, f.__name__
+    for f in (gfwd, gbwd):
+        assert f(n=0) == 1001 and f(n=4100) == 1001, f.__name__
+    assert keep(n=0) == 1001
+
+
 def test_packed_tile_gemm_and_patch_reject_bad_arguments():
     """The direct-B GEMM entry points, the dS patch and the loss head validate their shapes before
     launching anything (no GPU needed) -> TRIAD_EINVAL (1001)."""

@@ -1,6 +1,7 @@
 """GPU parity of the fused HuBERT post-LN passes (triad_amd.postln, csrc/postln.hip) against
 torch on the SAME dropout masks (the kernels' keep bits exposed by triad_dropout_keep), and of
-the fused encoder against the stock transformers encoder with dropout off."""
+the fused encoder against the stock transformers encoder with dropout off. The per-element
+conformance of the same kernels against fp64 is tests/test_postln_conformance_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -286,6 +286,14 @@ __global__ __launch_bounds__(256) void dropout_keep_kernel(long long n, unsigned
 
 unsigned drop_thr(float p) { return triad_drop_thr(p); }
 
+// Argument rules of the entry points below, checked before any launch. ptr_ok: non-NULL and aligned
+// to `a` bytes (a power of two): 16 for what a lane reads or writes as f32x4 / bf16x8 (fp32 row
+// tensors, w, b, the GELU operands and table), 8 for the bf16x4 of a bf16 row tensor, 4 for the
+// scalar fp32 stores (mean, rstd, part). opt_ok: the same for a pointer that may be NULL.
+bool ptr_ok(const void* p, uintptr_t a) { return p && !((uintptr_t)p & (a - 1)); }
+bool opt_ok(const void* p, uintptr_t a) { return !((uintptr_t)p & (a - 1)); }
+bool p_ok(float p) { return p >= 0.f && p < 1.f; }  // false for NaN
+
 }  // namespace
 
 extern "C" {
@@ -293,7 +301,10 @@ extern "C" {
 // h = LN(res + dropout(y)) fp32 and hb = bf16(h); res fp32 [M][D], y bf16 [M][D]; D % 256 == 0.
 int triad_dropaddln_fwd(const float* res, const void* y, const float* w, const float* b, float eps, int M, int D,
                         float p, unsigned seed, float* h, void* hb, float* mean, float* rstd, hipStream_t stream) {
-  if (M <= 0 || D % 256 || D > 1024 || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (M <= 0 || D <= 0 || D % 256 || D > 1024 || !p_ok(p) || !(eps > 0.f && eps < __builtin_inff())) return TRIAD_EINVAL;
+  if (!ptr_ok(res, 16) || !ptr_ok(h, 16) || !ptr_ok(w, 16) || !ptr_ok(b, 16) || !ptr_ok(y, 8) || !ptr_ok(hb, 8) ||
+      !ptr_ok(mean, 4) || !ptr_ok(rstd, 4))
+    return TRIAD_EINVAL;
   const float scale = 1.f / (1.f - p);
   const dim3 grid((M + 3) / 4);
 #define DAL_F(NB)                                                                                                  \
@@ -315,7 +326,10 @@ int triad_dropaddln_bwd_blocks(int M) { return M < 4 * 1024 ? (M + 3) / 4 : 1024
 int triad_dropaddln_bwd(const float* dh, const void* dhb, const float* res, const void* y, const float* mean,
                         const float* rstd, const float* w, int M, int D, float p, unsigned seed, float* dres, void* dy,
                         float* part, hipStream_t stream) {
-  if (M <= 0 || D % 256 || D > 1024 || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (M <= 0 || D <= 0 || D % 256 || D > 1024 || !p_ok(p)) return TRIAD_EINVAL;
+  if (!opt_ok(dh, 16) || !opt_ok(dhb, 8) || !ptr_ok(res, 16) || !ptr_ok(y, 8) || !ptr_ok(mean, 4) || !ptr_ok(rstd, 4) ||
+      !ptr_ok(w, 16) || !ptr_ok(dres, 16) || !ptr_ok(dy, 8) || !ptr_ok(part, 4))
+    return TRIAD_EINVAL;
   const float scale = 1.f / (1.f - p);
   const dim3 grid(triad_dropaddln_bwd_blocks(M));
 #define DAL_B(NB)                                                                                                  \
@@ -335,7 +349,7 @@ int triad_dropaddln_bwd(const float* dh, const void* dhb, const float* res, cons
 long long triad_gelu_table_bytes(void) { return GL_BYTES; }
 
 int triad_gelu_table(void* table, hipStream_t stream) {
-  if (!table) return TRIAD_EINVAL;
+  if (!ptr_ok(table, 16)) return TRIAD_EINVAL;
   hipLaunchKernelGGL(gelu_table_kernel, dim3((GL_N + 255) / 256), dim3(256), 0, stream, (float*)table,
                      (bf16*)((char*)table + GL_N * 4));
   TRIAD_CHECK_LAUNCH();
@@ -345,7 +359,7 @@ int triad_gelu_table(void* table, hipStream_t stream) {
 // v = dropout(gelu(u)) over n bf16 elements (n % 8 == 0); p = 0: plain exact-erf GELU (aten's roundings)
 int triad_geludrop_fwd(const void* u, long long n, float p, unsigned seed, const void* table, void* v,
                        hipStream_t stream) {
-  if (n <= 0 || n % 8 || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (n <= 0 || n % 8 || !p_ok(p) || !ptr_ok(u, 16) || !ptr_ok(v, 16) || !opt_ok(table, 16)) return TRIAD_EINVAL;
   const bf16* tv = table ? (const bf16*)((const char*)table + GL_N * 4) : nullptr;
   auto kern = p > 0.f ? (table ? geludrop_fwd_kernel<true, true> : geludrop_fwd_kernel<true, false>)
                       : (table ? geludrop_fwd_kernel<false, true> : geludrop_fwd_kernel<false, false>);
@@ -357,7 +371,8 @@ int triad_geludrop_fwd(const void* u, long long n, float p, unsigned seed, const
 
 int triad_geludrop_bwd(const void* u, const void* dv, long long n, float p, unsigned seed, const void* table, void* du,
                        hipStream_t stream) {
-  if (n <= 0 || n % 8 || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (n <= 0 || n % 8 || !p_ok(p) || !ptr_ok(u, 16) || !ptr_ok(dv, 16) || !ptr_ok(du, 16) || !opt_ok(table, 16))
+    return TRIAD_EINVAL;
   auto kern = p > 0.f ? (table ? geludrop_bwd_kernel<true, true> : geludrop_bwd_kernel<true, false>)
                       : (table ? geludrop_bwd_kernel<false, true> : geludrop_bwd_kernel<false, false>);
   hipLaunchKernelGGL(kern, dim3(gl_blocks(n)), dim3(GL_NT), 0, stream, (const bf16*)u, (const bf16*)dv, n, seed,
@@ -368,7 +383,7 @@ int triad_geludrop_bwd(const void* u, const void* dv, long long n, float p, unsi
 
 // keep bit of each of n elements (u8 0 / 1) for the given seed and p (test / debug view of the masks)
 int triad_dropout_keep(long long n, float p, unsigned seed, void* out, hipStream_t stream) {
-  if (n <= 0 || p < 0.f || p >= 1.f) return TRIAD_EINVAL;
+  if (n <= 0 || !p_ok(p) || !out) return TRIAD_EINVAL;
   hipLaunchKernelGGL(dropout_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, seed,
                      drop_thr(p), (unsigned char*)out);
   TRIAD_CHECK_LAUNCH();

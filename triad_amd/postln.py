@@ -37,6 +37,17 @@ class _Seeds:
         return int(torch.randint(0, 2 ** 32 - 1, (1,), generator=self.gen))
 
 
+def _dense(t, align):
+    """t as the kernels read it: contiguous, with a data pointer aligned to `align` bytes (their
+    vector accesses). Anything else is copied (.contiguous() keeps an offset view as it is)."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    if t.data_ptr() % align:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 class _DropAddLN(torch.autograd.Function):
     """(h, hb) = (LN(res + dropout(y)), bf16 copy); res fp32 [..., D], y bf16 [..., D]."""
 
@@ -48,8 +59,7 @@ class _DropAddLN(torch.autograd.Function):
         if not (res.dtype == torch.float32 and y.dtype == torch.bfloat16 and y.shape == res.shape
                 and w.dtype == b.dtype == torch.float32 and w.numel() == b.numel() == D):
             raise TypeError(f"drop_add_ln: res {res.dtype} {tuple(res.shape)}, y {y.dtype} {tuple(y.shape)}")
-        res = res.contiguous()
-        y = y.contiguous()
+        res, y, w, b = _dense(res, 16), _dense(y, 8), _dense(w, 16), _dense(b, 16)
         h = torch.empty_like(res)
         hb = torch.empty(res.shape, dtype=torch.bfloat16, device=dev)
         mean = torch.empty(M, dtype=torch.float32, device=dev)
@@ -67,8 +77,7 @@ class _DropAddLN(torch.autograd.Function):
         D = res.shape[-1]
         M = res.numel() // D
         dev = res.device
-        dh = None if dh is None else dh.contiguous()
-        dhb = None if dhb is None else dhb.contiguous()
+        dh, dhb = _dense(dh, 16), _dense(dhb, 8)
         if (dh is not None and (dh.dtype != torch.float32 or dh.shape != res.shape)) or \
                 (dhb is not None and (dhb.dtype != torch.bfloat16 or dhb.shape != res.shape)):
             raise TypeError("drop_add_ln backward: unexpected gradient layout")
@@ -106,7 +115,7 @@ class _GeluDrop(torch.autograd.Function):
     def forward(ctx, u, p, seed):
         if u.dtype != torch.bfloat16 or u.numel() % 8:
             raise TypeError(f"gelu_drop: u {u.dtype} {tuple(u.shape)}")
-        u = u.contiguous()
+        u = _dense(u, 16)
         v = torch.empty_like(u)
         call("triad_geludrop_fwd", ptr(u), u.numel(), p, seed, ptr(gelu_table(u.device)), ptr(v),
              stream_ptr(u.device))
@@ -118,7 +127,7 @@ class _GeluDrop(torch.autograd.Function):
     def backward(ctx, dv):
         (u,) = ctx.saved_tensors
         p, seed = ctx.meta
-        dv = dv.to(torch.bfloat16).contiguous()
+        dv = _dense(dv.to(torch.bfloat16), 16)
         du = torch.empty_like(u)
         call("triad_geludrop_bwd", ptr(u), ptr(dv), u.numel(), p, seed, ptr(gelu_table(u.device)), ptr(du),
              stream_ptr(u.device))
