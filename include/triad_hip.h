@@ -445,8 +445,9 @@ int triad_posconv_dw(const void* x, const void* dy, int B, int T, int C, int gro
  * D != 64, B*H > 65535 (one grid row per (sample, head)); a scale that is not finite or <= 0 (the
  * row max is taken over the unscaled scores); a null or not 16-byte aligned q, k, v, out, o, dout,
  * dq, dk or dv; an sB or sN that is not a multiple of 8 elements (rows are read and written as
- * 16- and 8-byte vectors); a null lse, or a null delta in the backward; p outside [0, 1); one of
- * wq, wk null and the other not. */
+ * 16- and 8-byte vectors); a null lse, or a null delta in the backward; p outside [0, 1) or NaN;
+ * one of wq, wk null and the other not (backward), either null (triad_attn_dropmask). The masks need
+ * no more than their 4-byte alignment here: these kernels read one word at a time. */
 int triad_attn_fwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
                    const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D, float scale, void* out,
                    long long out_sB, long long out_sN, float* lse, hipStream_t stream);

@@ -7,6 +7,7 @@ figures."""
 import pytest
 import torch
 
+from tests import attention_abi as ABI
 from tests import attention_ref as R
 
 B, H = 2, 3
@@ -171,6 +172,20 @@ def test_backward_bounds_see_a_planted_error(problems, name):
             if family == "gauss":
                 _note_planted(name, r)
                 assert not _ok(r), (name, N, r)
+
+
+@pytest.mark.parametrize("which", ["fwd", "bwd"])
+@pytest.mark.parametrize("family", ["short", "short, no dropout"])
+def test_forward_and_backward_reject_bad_arguments(family, which):
+    """Every TRIAD_EINVAL rule of triad_attn_fwd_dropout / _bwd_dropout and of triad_attn_fwd / _bwd
+    (tests/attention_abi.py; validation comes before any launch, so no device is needed). That this
+    family accepts keep words at a 4-byte offset cannot be shown here: an accepted call launches."""
+    ABI.forward_or_backward_rejects_bad_arguments(family, which)
+
+
+def test_dropmask_rejects_bad_arguments():
+    """triad_attn_dropmask: the sizes, p (NaN included) and a null wq or wk."""
+    ABI.dropmask_rejects_bad_arguments("short")
 
 
 def test_wrapper_gates():

@@ -510,7 +510,10 @@ def _forbid_kernels(monkeypatch):
 
     def boom(*a, **k):
         raise AssertionError("the HIP forward was called for an unsupported input")
-    monkeypatch.setattr(A, "_fwd", boom)
+    monkeypatch.setattr(A, "_fwd", boom)   # the forward of both families
+    # N = 321 belongs to the streaming kernels by default (tests/test_attention_long_conformance_gpu.py);
+    # with their route closed it is PyTorch's, like everything else the whole-sequence kernels refuse
+    monkeypatch.setattr(A, "LONG_ROUTE", (A.MAX_TOKENS_LONG + 1, A.MAX_TOKENS_LONG))
 
 
 @pytest.mark.parametrize("why,N,d,dtype,scale", [("N = 321", 321, 64, BF, None), ("head dim 32", 40, 32, BF, None),

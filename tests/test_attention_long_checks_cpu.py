@@ -1,7 +1,7 @@
 """CPU checks for the streaming attention kernels of csrc/attention_long.hip (321 <= N <= 2048):
 
-* every TRIAD_EINVAL rule of triad_attn_long_fwd / _bwd / _dropmask, one assertion per rule (the
-  library validates before it launches, so no device is needed);
+* every TRIAD_EINVAL rule of triad_attn_long_fwd / _bwd / _dropmask, one assertion per rule
+  (tests/attention_abi.py: the library validates before it launches, so no device is needed);
 * attention.supported_long, LONG_ROUTE and the routing of the wrappers at N = 320, 321, 2048, 2049;
 * the checks of tests/test_attention_long_conformance_gpu.py bite: the chunked fp32 / bf16 emulations
   of the three kernels (tests/attention_long_ref.py) pass every per-element bound on the five input
@@ -11,12 +11,12 @@ B = 2, H = 3 up to N = 499; B = 1, H = 2 at N = 1374 (the fp64 references stay u
 import pytest
 import torch
 
+from tests import attention_abi as ABI
 from tests import attention_long_ref as LR
 from tests import attention_ref as R
 
 SCALE = R.f32(R.SCALE)
 SIZES = (321, 499, 1374)
-EINVAL = 1001
 CLEAN, PLANTED = {}, {}
 
 
@@ -26,85 +26,13 @@ def _bh(N):
 
 # ---- the entry points' argument checks -------------------------------------------------------------
 
-def _lib():
-    from triad_amd import _lib
-    return _lib.load()
-
-
-FAKE = 4096   # 16-byte aligned, never dereferenced: validation fails first
-
-
-def _fwd(lib, **over):
-    a = dict(q=(FAKE, 1 << 20, 192), k=(FAKE, 1 << 20, 192), v=(FAKE, 1 << 20, 192), B=2, H=3, N=499, D=64,
-             scale=0.125, wq=None, p=0.0, out=(FAKE, 1 << 20, 192), lse=FAKE)
-    a.update(over)
-    return lib.triad_attn_long_fwd(*a["q"], *a["k"], *a["v"], a["B"], a["H"], a["N"], a["D"], a["scale"], a["wq"],
-                                   a["p"], *a["out"], a["lse"], None)
-
-
-def _bwd(lib, **over):
-    t = (FAKE, 1 << 20, 192)
-    a = dict(q=t, k=t, v=t, o=t, do=t, dq=t, dk=t, dv=t, lse=FAKE, delta=FAKE, B=2, H=3, N=499, D=64, scale=0.125,
-             wq=None, wk=None, p=0.0)
-    a.update(over)
-    return lib.triad_attn_long_bwd(*a["q"], *a["k"], *a["v"], *a["o"], *a["do"], a["lse"], a["B"], a["H"], a["N"],
-                                   a["D"], a["scale"], a["wq"], a["wk"], a["p"], *a["dq"], *a["dk"], *a["dv"],
-                                   a["delta"], None)
-
-
-def _mask(lib, B=2, H=3, N=499, p=0.1, wq=FAKE, wk=FAKE):
-    return lib.triad_attn_long_dropmask(B, H, N, p, 7, wq, wk, None)
-
-
 @pytest.mark.parametrize("which", ["fwd", "bwd"])
 def test_forward_and_backward_reject_bad_arguments(which):
-    lib = _lib()
-    f = (lambda **kw: _fwd(lib, **kw)) if which == "fwd" else (lambda **kw: _bwd(lib, **kw))
-    tensors = ("q", "k", "v", "out") if which == "fwd" else ("q", "k", "v", "o", "do", "dq", "dk", "dv")
-    assert f(N=320) == EINVAL
-    assert f(N=2049) == EINVAL
-    assert f(N=0) == EINVAL
-    assert f(D=32) == EINVAL
-    assert f(D=128) == EINVAL
-    assert f(B=0) == EINVAL
-    assert f(H=0) == EINVAL
-    assert f(B=-1) == EINVAL
-    assert f(B=257, H=256) == EINVAL                       # B * H = 65792
-    for s in (0.0, -0.125, float("inf"), float("-inf"), float("nan")):
-        assert f(scale=s) == EINVAL, s
-    for p in (-0.1, 1.0, 1.5, float("nan")):
-        assert f(p=p) == EINVAL, p
-    for t in tensors:
-        assert f(**{t: (None, 1 << 20, 192)}) == EINVAL, t          # null
-        assert f(**{t: (FAKE + 8, 1 << 20, 192)}) == EINVAL, t      # 8-byte aligned only
-        assert f(**{t: (FAKE + 2, 1 << 20, 192)}) == EINVAL, t
-        assert f(**{t: (FAKE, (1 << 20) + 4, 192)}) == EINVAL, t    # sB % 8
-        assert f(**{t: (FAKE, 1 << 20, 196)}) == EINVAL, t          # sN % 8
-        assert f(**{t: (FAKE, 1 << 20, 193)}) == EINVAL, t
-    assert f(lse=None) == EINVAL
-    if which == "fwd":
-        assert f(wq=FAKE + 4, p=0.1) == EINVAL                      # keep words are read two at a time
-    else:
-        assert f(delta=None) == EINVAL
-        assert f(wq=FAKE, wk=None, p=0.1) == EINVAL                 # one mask without the other
-        assert f(wq=None, wk=FAKE, p=0.1) == EINVAL
-        assert f(wq=FAKE + 4, wk=FAKE, p=0.1) == EINVAL
-        assert f(wq=FAKE, wk=FAKE + 4, p=0.1) == EINVAL
+    ABI.forward_or_backward_rejects_bad_arguments("long", which)
 
 
 def test_dropmask_rejects_bad_arguments():
-    lib = _lib()
-    assert _mask(lib, N=320) == EINVAL
-    assert _mask(lib, N=2049) == EINVAL
-    assert _mask(lib, B=0) == EINVAL
-    assert _mask(lib, H=0) == EINVAL
-    assert _mask(lib, B=257, H=256) == EINVAL
-    for p in (-0.1, 1.0, float("nan")):
-        assert _mask(lib, p=p) == EINVAL, p
-    assert _mask(lib, wq=None) == EINVAL
-    assert _mask(lib, wk=None) == EINVAL
-    assert _mask(lib, wq=FAKE + 4) == EINVAL
-    assert _mask(lib, wk=FAKE + 4) == EINVAL
+    ABI.dropmask_rejects_bad_arguments("long")
 
 
 def test_new_entry_points_are_backbone_only():
@@ -151,23 +79,18 @@ class _Stub(torch.Tensor):
 
 @pytest.mark.parametrize("N,want", [(320, "short"), (321, "long"), (2048, "long"), (2049, "torch")])
 def test_routing(monkeypatch, N, want):
-    """sdpa, hf_attention_forward and vit.Attention with _fwd / _fwd_long patched: 320 tokens take
-    the whole-sequence kernels, 321 and 2048 the streaming ones (if LONG_ROUTE holds them), 2049
-    PyTorch."""
+    """sdpa, hf_attention_forward and vit.Attention with the library call patched (every entry point
+    that reaches attention.call is recorded): 320 tokens take the whole-sequence forward, 321 and 2048
+    the streaming one (if LONG_ROUTE holds them), 2049 PyTorch; one forward per call, nothing else."""
     from triad_amd import attention as A
     from triad_amd import vit
     if want == "long" and not A.LONG_ROUTE[0] <= N <= A.LONG_ROUTE[1]:
         want = "torch"
     calls = []
-
-    def fake(name):
-        def f(q, k, v, scale, drop=None):
-            calls.append(name)
-            B, n, H, D = q.shape
-            return torch.zeros(B, n, H, D, dtype=torch.bfloat16), torch.zeros(B * H, n)
-        return f
-    monkeypatch.setattr(A, "_fwd", fake("short"))
-    monkeypatch.setattr(A, "_fwd_long", fake("long"))
+    family = {"triad_attn_fwd_dropout": "short", "triad_attn_long_fwd": "long"}
+    monkeypatch.setattr(A, "call", lambda name, *args: calls.append(family.get(name, name)))
+    monkeypatch.setattr(A, "ptr", lambda t: None)
+    monkeypatch.setattr(A, "stream_ptr", lambda device=None: None)
     monkeypatch.setattr(A.F, "scaled_dot_product_attention",
                         lambda q, k, v, **kw: (calls.append("torch"), torch.zeros_like(q))[1])
     monkeypatch.setattr(A, "_as_bnhd", lambda t: t)

@@ -413,10 +413,16 @@ def _rel(a, b):
 
 
 def _count_long(monkeypatch):
+    """Counts the streaming forwards (triad_attn_long_fwd) that reach attention.call."""
     from triad_amd import attention as A
     calls = []
-    real = A._fwd_long
-    monkeypatch.setattr(A, "_fwd_long", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    real = A.call
+
+    def call(name, *a, **k):
+        if name == "triad_attn_long_fwd":
+            calls.append(1)
+        return real(name, *a, **k)
+    monkeypatch.setattr(A, "call", call)
     return calls
 
 
@@ -466,8 +472,8 @@ def _module():
 
 @pytest.mark.parametrize("N", [1374, 2049])
 def test_sdpa_hf_and_vit_take_the_streaming_kernels_up_to_2048(monkeypatch, N):
-    """sdpa, hf_attention_forward and vit.Attention (dim 128, 2 heads) at N = 1374 each call _fwd_long
-    once (if LONG_ROUTE holds 1374) and match fp32 math to 1e-2 relative L2; at N = 2049 none calls
+    """sdpa, hf_attention_forward and vit.Attention (dim 128, 2 heads) at N = 1374 each call
+    triad_attn_long_fwd once (if LONG_ROUTE holds 1374) and match fp32 math to 1e-2 relative L2; at N = 2049 none calls
     it and all still match."""
     from triad_amd import attention as A
     from triad_amd import vit

@@ -7,9 +7,11 @@ Both run in one process, alternating round by round after a warm-up of each (cod
 PyTorch's kernel choice made); each round times ITERS forward + backward passes with HIP events.
 Reported per shape: the median over the rounds, the run-to-run spread (max - min) / median of each
 side, and the ratio of the medians. DESIGN.md section 5 holds the rule that reads these numbers
-(attention.LONG_ROUTE).
+(attention.LONG_ROUTE). --shapes times other (B, H, N, p), the short family's included (N <= 320 runs
+csrc/attention.hip); run under TRIAD_LIB_VARIANT it times another build of the library.
 
-    python tools/attn_long_time.py [--rounds 9] [--iters 10] > profiles/attn_long_time.log
+    python tools/attn_long_time.py [--rounds 9] [--iters 10] [--shapes 32x16x261x0,32x16x199x0.1]
+        > profiles/attn_long_time.log
 """
 import argparse
 import os
@@ -48,15 +50,20 @@ def _time(fn, args, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def _shapes(text):
+    return tuple((int(b), int(h), int(n), float(p)) for b, h, n, p in (s.split("x") for s in text.split(",")))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--shapes", type=_shapes, default=SHAPES, help="BxHxNxp,... (default: the c5 shapes)")
     a = ap.parse_args()
     torch.manual_seed(0)
     print(f"device {torch.cuda.get_device_name(0)}; LONG_ROUTE {A.LONG_ROUTE}; rounds {a.rounds} x iters {a.iters}, "
           "ms per forward + backward")
-    for B, H, N, p in SHAPES:
+    for B, H, N, p in a.shapes:
         q, k, v = (torch.randn(B, N, H, 64, device="cuda").mul_(1.5).to(torch.bfloat16).requires_grad_(True)
                    for _ in range(3))
         do = torch.randn(B, N, H, 64, device="cuda").to(torch.bfloat16)

@@ -1,4 +1,4 @@
-"""Backbone self-attention on the HIP kernels of csrc/attention.hip.
+"""Backbone self-attention on the HIP kernels of csrc/attention.hip and csrc/attention_long.hip.
 
 The reference's encoders (SajayR/TRIAD model.py:29-30,79-80,218-227: DINOv2, HuBERT,
 DistilBERT) run softmax(Q K^T * scale) V over short sequences -- 261 visual tokens, 199 audio
@@ -12,8 +12,10 @@ Longer sequences, 321 .. 2048 tokens (configuration c5: 1374 visual tokens of DI
 518 px, 499 audio frames of HuBERT-large on 10 s), take the streaming kernels of
 csrc/attention_long.hip: K / V (or Q / dO) pass through LDS in chunks of 64 rows and the forward
 keeps an online softmax per query; same tensors, same dropout bits, words padded to whole chunks.
-Which token counts are routed there is LONG_ROUTE. Anything else -- masks, causal attention, head
-dim != 64, fp32, N > 2048 -- goes to F.scaled_dot_product_attention.
+Both families have one C signature per step, so one _fwd / _bwd / _dropmask serves them: _is_long(N)
+picks the entry points (_ENTRY) and the words per mask row. Which token counts are routed to the
+streaming kernels is LONG_ROUTE. Anything else -- masks, causal attention, head dim != 64, fp32,
+N > 2048 -- goes to F.scaled_dot_product_attention.
 """
 from __future__ import annotations
 
@@ -31,26 +33,35 @@ MAX_SEQUENCES = 65535   # B * H: one grid row per (sample, head)
 # token counts the wrappers send to the streaming kernels (inclusive). The entry points accept all of
 # 321 .. 2048; narrow this only where a measurement shows PyTorch's kernels ahead
 LONG_ROUTE = (321, 2048)
+# (dropmask, forward, backward) entry points by _is_long(N)
+_ENTRY = {False: ("triad_attn_dropmask", "triad_attn_fwd_dropout", "triad_attn_bwd_dropout"),
+          True: ("triad_attn_long_dropmask", "triad_attn_long_fwd", "triad_attn_long_bwd")}
+
+
+def _gate(x, n, lo, hi, head_dim, scale, sequences):
+    if scale is not None and not (math.isfinite(scale) and scale > 0.0):
+        return False
+    return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and lo <= n <= hi
+            and 0 < sequences <= MAX_SEQUENCES)
 
 
 def supported(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int = 1) -> bool:
     """What the entry points accept (they return TRIAD_EINVAL otherwise): bf16 on the device, head
     dim 64, 1 .. 320 tokens, at most 65535 (sample, head) sequences, a finite scale > 0 (None = the
     default 1 / sqrt(head dim)). The kernels take the row max of the unscaled scores."""
-    if scale is not None and not (math.isfinite(scale) and scale > 0.0):
-        return False
-    return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and 0 < n <= MAX_TOKENS
-            and 0 < sequences <= MAX_SEQUENCES)
+    return _gate(x, n, 1, MAX_TOKENS, head_dim, scale, sequences)
 
 
 def supported_long(x: torch.Tensor, n: int, head_dim: int, scale=None, sequences: int = 1) -> bool:
     """What the wrappers send to the streaming kernels (triad_attn_long_*): as `supported`, with
     LONG_ROUTE[0] <= n <= LONG_ROUTE[1] tokens (inside the entry points' 321 .. 2048)."""
-    if scale is not None and not (math.isfinite(scale) and scale > 0.0):
-        return False
-    lo, hi = max(LONG_ROUTE[0], MAX_TOKENS + 1), min(LONG_ROUTE[1], MAX_TOKENS_LONG)
-    return (x.is_cuda and x.dtype == torch.bfloat16 and head_dim == HEAD_DIM and lo <= n <= hi
-            and 0 < sequences <= MAX_SEQUENCES)
+    return _gate(x, n, max(LONG_ROUTE[0], MAX_TOKENS + 1), min(LONG_ROUTE[1], MAX_TOKENS_LONG), head_dim, scale,
+                 sequences)
+
+
+def takes(x: torch.Tensor, B: int, H: int, n: int, head_dim: int, scale=None) -> bool:
+    """Do the HIP kernels (either family) take B * H sequences of n tokens of x's kind?"""
+    return supported(x, n, head_dim, scale, B * H) or supported_long(x, n, head_dim, scale, B * H)
 
 
 def _rows(t):
@@ -68,31 +79,25 @@ def _as_bnhd(t):
     return t
 
 
-def _dropmask(B, H, N, p, device):
-    """Keep bits of the attention-probability dropout in both layouts (triad_attn_dropmask)."""
-    nkt = (N + 31) // 32
-    wq = torch.empty(B * H * N * nkt, dtype=torch.int32, device=device)
-    wk = torch.empty_like(wq)
-    call("triad_attn_dropmask", B, H, N, float(p), _SEEDS(), ptr(wq), ptr(wk), stream_ptr(device))
-    return wq, wk
-
-
-def _dropmask_long(B, H, N, p, device):
-    """The same keep bits for the streaming kernels: 2 ceil(N / 64) words per row (triad_attn_long_dropmask)."""
-    wpr = 2 * ((N + 63) // 64)
-    wq = torch.empty(B * H * N * wpr, dtype=torch.int32, device=device)
-    wk = torch.empty_like(wq)
-    call("triad_attn_long_dropmask", B, H, N, float(p), _SEEDS(), ptr(wq), ptr(wk), stream_ptr(device))
-    return wq, wk
-
-
 def _is_long(N):
-    """Which pair of kernels _Attention / _AttentionQKV run: the streaming ones past MAX_TOKENS."""
+    """Which family _Attention / _AttentionQKV run: the streaming kernels past MAX_TOKENS."""
     return N > MAX_TOKENS
 
 
-def _draw_mask(B, H, N, p, device):
-    return (_dropmask_long if _is_long(N) else _dropmask)(B, H, N, p, device)
+def _words_per_row(N):
+    """Keep words per mask row: ceil(N / 32), or 2 ceil(N / 64) for the streaming kernels (rows padded
+    to whole 64-row chunks)."""
+    return 2 * ((N + 63) // 64) if _is_long(N) else (N + 31) // 32
+
+
+def _dropmask(B, H, N, p, device, seed=None):
+    """Keep bits of the attention-probability dropout in both layouts (triad_attn[_long]_dropmask);
+    seed None = one draw from _SEEDS."""
+    wq = torch.empty(B * H * N * _words_per_row(N), dtype=torch.int32, device=device)
+    wk = torch.empty_like(wq)
+    call(_ENTRY[_is_long(N)][0], B, H, N, float(p), _SEEDS() if seed is None else seed, ptr(wq), ptr(wk),
+         stream_ptr(device))
+    return wq, wk
 
 
 def _fwd(q, k, v, scale, drop=None):
@@ -100,7 +105,7 @@ def _fwd(q, k, v, scale, drop=None):
     out = torch.empty(B, N, H, D, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
     wq, p = (drop[0], drop[2]) if drop is not None else (None, 0.0)
-    call("triad_attn_fwd_dropout", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), B, H, N, D, float(scale),
+    call(_ENTRY[_is_long(N)][1], ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), B, H, N, D, float(scale),
          ptr(wq), float(p), ptr(out), *_rows(out), ptr(lse), stream_ptr(q.device))
     return out, lse
 
@@ -113,32 +118,7 @@ def _bwd(q, k, v, out, lse, dout, scale, drop=None):
     dq, dk, dv = g[:, :, 0], g[:, :, 1], g[:, :, 2]
     delta = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
     wq, wk, p = drop if drop is not None else (None, None, 0.0)
-    call("triad_attn_bwd_dropout", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), ptr(out), *_rows(out),
-         ptr(do), *_rows(do), ptr(lse), B, H, N, D, float(scale), ptr(wq), ptr(wk), float(p), ptr(dq), *_rows(dq),
-         ptr(dk), *_rows(dk), ptr(dv), *_rows(dv), ptr(delta), stream_ptr(q.device))
-    return g
-
-
-def _fwd_long(q, k, v, scale, drop=None):
-    """_fwd on the streaming kernels (321 <= N <= 2048)."""
-    B, N, H, D = q.shape
-    out = torch.empty(B, N, H, D, dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
-    wq, p = (drop[0], drop[2]) if drop is not None else (None, 0.0)
-    call("triad_attn_long_fwd", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), B, H, N, D, float(scale),
-         ptr(wq), float(p), ptr(out), *_rows(out), ptr(lse), stream_ptr(q.device))
-    return out, lse
-
-
-def _bwd_long(q, k, v, out, lse, dout, scale, drop=None):
-    """_bwd on the streaming kernels: the same (B, N, 3, H, 64) gradient buffer."""
-    B, N, H, D = q.shape
-    do = _as_bnhd(dout.to(torch.bfloat16))
-    g = torch.empty(B, N, 3, H, D, dtype=torch.bfloat16, device=q.device)
-    dq, dk, dv = g[:, :, 0], g[:, :, 1], g[:, :, 2]
-    delta = torch.empty(B * H, N, dtype=torch.float32, device=q.device)
-    wq, wk, p = drop if drop is not None else (None, None, 0.0)
-    call("triad_attn_long_bwd", ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), ptr(out), *_rows(out),
+    call(_ENTRY[_is_long(N)][2], ptr(q), *_rows(q), ptr(k), *_rows(k), ptr(v), *_rows(v), ptr(out), *_rows(out),
          ptr(do), *_rows(do), ptr(lse), B, H, N, D, float(scale), ptr(wq), ptr(wk), float(p), ptr(dq), *_rows(dq),
          ptr(dk), *_rows(dk), ptr(dv), *_rows(dv), ptr(delta), stream_ptr(q.device))
     return g
@@ -161,8 +141,8 @@ class _Attention(torch.autograd.Function):
         drop = None
         if p > 0.0:
             B, N, H, _ = q.shape
-            drop = (*_draw_mask(B, H, N, p, q.device), float(p))
-        out, lse = (_fwd_long if _is_long(q.shape[1]) else _fwd)(q, k, v, scale, drop)
+            drop = (*_dropmask(B, H, N, p, q.device), float(p))
+        out, lse = _fwd(q, k, v, scale, drop)
         ctx.save_for_backward(q, k, v, out, lse, *(drop[:2] if drop else ()))
         ctx.scale = float(scale)
         ctx.p = float(p)
@@ -173,7 +153,7 @@ class _Attention(torch.autograd.Function):
         saved = ctx.saved_tensors
         q, k, v, out, lse = saved[:5]
         drop = (saved[5], saved[6], ctx.p) if ctx.p > 0.0 else None
-        g = (_bwd_long if _is_long(q.shape[1]) else _bwd)(q, k, v, out, lse, dout, ctx.scale, drop)
+        g = _bwd(q, k, v, out, lse, dout, ctx.scale, drop)
         return g[:, :, 0], g[:, :, 1], g[:, :, 2], None, None
 
 
@@ -190,8 +170,8 @@ class _AttentionQKV(torch.autograd.Function):
             x = x.clone()
         x = x.view(B, N, 3, heads, HEAD_DIM)
         q, k, v = x[:, :, 0], x[:, :, 1], x[:, :, 2]
-        drop = (*_draw_mask(B, heads, N, p, qkv.device), float(p)) if p > 0.0 else None
-        out, lse = (_fwd_long if _is_long(N) else _fwd)(q, k, v, scale, drop)
+        drop = (*_dropmask(B, heads, N, p, qkv.device), float(p)) if p > 0.0 else None
+        out, lse = _fwd(q, k, v, scale, drop)
         ctx.save_for_backward(x, out, lse, *(drop[:2] if drop else ()))
         ctx.scale = float(scale)
         ctx.p = float(p)
@@ -203,8 +183,7 @@ class _AttentionQKV(torch.autograd.Function):
         x, out, lse = saved[:3]
         drop = (saved[3], saved[4], ctx.p) if ctx.p > 0.0 else None
         B, N = x.shape[0], x.shape[1]
-        g = (_bwd_long if _is_long(N) else _bwd)(x[:, :, 0], x[:, :, 1], x[:, :, 2], out, lse, dout.view(out.shape),
-                                                 ctx.scale, drop)
+        g = _bwd(x[:, :, 0], x[:, :, 1], x[:, :, 2], out, lse, dout.view(out.shape), ctx.scale, drop)
         return g.view(B, N, -1), None, None, None
 
 
@@ -225,14 +204,11 @@ def attention_bnhd(q, k, v, scale=None, dropout=0.0):
 def dropout_keep_dense(B, H, N, p, seed, device):
     """(B, H, N, N) keep mask (bool) of the attention dropout for a given seed, unpacked from both
     stored layouts (tests: the two must agree)."""
-    nkt = (N + 31) // 32
-    wq = torch.empty(B * H * N * nkt, dtype=torch.int32, device=device)
-    wk = torch.empty_like(wq)
-    call("triad_attn_dropmask", B, H, N, float(p), seed, ptr(wq), ptr(wk), stream_ptr(device))
+    wq, wk = _dropmask(B, H, N, p, device, seed)
     bits = torch.arange(32, device=device, dtype=torch.int32)
 
     def unpack(w):
-        m = ((w.view(B, H, N, nkt, 1) >> bits) & 1).bool().view(B, H, N, nkt * 32)
+        m = ((w.view(B, H, N, -1, 1) >> bits) & 1).bool().view(B, H, N, -1)
         return m[..., :N]
     return unpack(wq), unpack(wk).transpose(-1, -2)
 
@@ -241,8 +217,7 @@ def sdpa(q, k, v, scale=None):
     """F.scaled_dot_product_attention(q, k, v) (no mask / dropout) for (B, H, N, d) inputs: the
     HIP kernels when supported (<= 320 tokens, or LONG_ROUTE on the streaming kernels), else PyTorch."""
     B, H, N, d = q.shape
-    hip = supported(q, N, d, scale, B * H) or supported_long(q, N, d, scale, B * H)
-    if not hip or k.shape != q.shape or v.shape != q.shape:
+    if not takes(q, B, H, N, d, scale) or k.shape != q.shape or v.shape != q.shape:
         return F.scaled_dot_product_attention(q, k, v, scale=scale)
     o = attention_bnhd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), scale)
     return o.transpose(1, 2)
@@ -259,8 +234,7 @@ def hf_attention_forward(module, query, key, value, attention_mask, dropout=0.0,
     p = float(dropout) if module.training else 0.0
     if (attention_mask is not None or kwargs.get("output_attentions") or not 0.0 <= p < 1.0
             or key.shape != query.shape or value.shape != query.shape
-            or not (supported(query, N, d, scaling, B * H) or supported_long(query, N, d, scaling, B * H))
-            or getattr(module, "is_causal", False)):
+            or not takes(query, B, H, N, d, scaling) or getattr(module, "is_causal", False)):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)
     o = attention_bnhd(query.transpose(1, 2), key.transpose(1, 2), value.transpose(1, 2), scaling, dropout=p)

@@ -22,28 +22,12 @@
 // 4-row transposed reads.
 // Tensors are (B, N, H, 64) in memory with the head dimension contiguous: element (b, n, h, c)
 // at b * sB + n * sN + h * 64 + c (fused qkv projections and HF's transposed views alike).
+// This file holds the kernels and their launches only: the argument struct AttnArgs, the entry points'
+// checks and the tile helpers are in attention_tiles.h (shared with the streaming kernels of
+// attention_long.hip), the dropout keep words come from attention_mask.hip.
 #include "attention_tiles.h"
 
 namespace {
-
-constexpr int MAX_KT = 10;        // key / query tiles of 32 (N <= 320)
-
-struct AttnArgs {
-  const bf16 *q, *k, *v, *o, *dout;
-  long long q_sB, q_sN, k_sB, k_sN, v_sB, v_sN, o_sB, o_sN, do_sB, do_sN;
-  bf16 *out, *dq, *dk, *dv;
-  long long out_sB, out_sN, dq_sB, dq_sN, dk_sB, dk_sN, dv_sB, dv_sN;
-  float* lse;       // [B*H][N] natural-log log-sum-exp of the scaled scores
-  float* delta;     // [B*H][N] rowsum(dO * O)
-  int B, H, N;
-  float scale;
-  // dropout on the attention probabilities (DROP kernels): keep bits by query row
-  // wq[(bh * N + q) * nkt + kt] (bit j = key 32 kt + j) and by key row wk[(bh * N + key) * nkt + qt]
-  // (bit j = query 32 qt + j); kept probabilities scaled by drop_scale = 1 / (1 - p)
-  const unsigned *wq, *wk;
-  int nkt;
-  float drop_scale;
-};
 
 // rows [0, 32 NT) of two (b, h) slices into swizzled LDS, zero rows >= N. Every global load is
 // issued before the first LDS write (one latency, not one per row).
@@ -102,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   if (nlast < 32) {
 #pragma unroll
     for (int v = 0; v < 16; ++v)
-      if ((v & 3) + 8 * (v >> 2) + 4 * h >= nlast) acc[NKT - 1][v] = -INFINITY;
+      if (acc_row(v, h) >= nlast) acc[NKT - 1][v] = -INFINITY;
   }
   float m = -INFINITY;
 #pragma unroll
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_kernel(AttnArgs a) {
     const unsigned w = DROP && qok ? a.wq[((long long)bh * a.N + q) * NKT + kt] : 0u;
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const bool ok = qok && (v & 3) + 8 * (v >> 2) + 4 * h < nv;
+      const bool ok = qok && acc_row(v, h) < nv;
       const float e = __builtin_amdgcn_exp2f(fmaf(s[v], c2, -lse2));
       const float p = ok ? e : 0.f;
       const float dpv = DROP ? (tile_bit(w, v, h) ? dp[v] * a.drop_scale : 0.f) : dp[v];
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnArgs a) {
   // C[row = key (v&3)+8(v>>2)+4h][col = dim (lane&31)]
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int kr = kt * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+    const int kr = kt * 32 + acc_row(v, h);
     if (kr < a.N) {
       bf16* dkp = a.dk + b * a.dk_sB + (long long)kr * a.dk_sN + hh * HD + kl;
       bf16* dvp = a.dv + b * a.dv_sB + (long long)kr * a.dv_sN + hh * HD + kl;
@@ -323,87 +307,22 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnArgs a) {
     default: hipLaunchKernelGGL((KERNEL<10, DR>), GRID, dim3(256), 0, stream, ARGS); break;     \
   }
 
-// keep bits of the attention-probability dropout in both layouts (AttnArgs::wq / wk): bit of
-// (bh, q, key) = element e = (bh N + q) N + key of the (B H, N, N) probability tensor.
-// Block = one 32-query row band (query tile qt) of one (sample, head), all key tiles: thread
-// (row r, key tile kt) hashes its 16 element pairs into the wq word, the band's words meet in
-// LDS and thread (key row j, key tile kt) gathers bit j of the 32 words of tile kt into the wk
-// word of key kt * 32 + j (query bits of tile qt). (One 64-thread block per 32 x 32 tile, 32
-// threads busy per phase, made this a 90 us launch at HuBERT's shape.)
-__global__ __launch_bounds__(256) void attn_dropmask_kernel(int N, int nkt, unsigned seed, unsigned thr,
-                                                            unsigned* __restrict__ wq, unsigned* __restrict__ wk) {
-  __shared__ unsigned words[MAX_KT][33];
-  const int qt = blockIdx.x;
-  const long long bh = blockIdx.y;
-  for (int t = threadIdx.x; t < 32 * nkt; t += 256) {
-    const int r = t & 31, kt = t >> 5, q = qt * 32 + r;
-    unsigned bits = 0u;
-    if (q < N) {
-      const unsigned long long e0 = (unsigned long long)((bh * N + q) * N + kt * 32);
-      const int ncol = min(32, N - kt * 32);
-      // pairs covering elements e0 .. e0 + ncol - 1
-      const unsigned long long p0 = e0 >> 1;
-      const int off = (int)(e0 & 1);
-      unsigned long long stream = 0ull;  // bit i = element e0 - off + i
-      const int npairs = (ncol + off + 1) >> 1;
-#pragma unroll
-      for (int i = 0; i < 17; ++i)  // constant shifts (npairs <= 17)
-        if (i < npairs) stream |= (unsigned long long)keep_pair(p0 + i, seed, thr) << (2 * i);
-      bits = (unsigned)(stream >> off);
-      if (ncol < 32) bits &= (1u << ncol) - 1u;
-      wq[(bh * N + q) * nkt + kt] = bits;
-    }
-    words[kt][r] = bits;
-  }
-  __syncthreads();
-  for (int t = threadIdx.x; t < 32 * nkt; t += 256) {
-    const int j = t & 31, kt = t >> 5;  // key row kt * 32 + j: bit i = query qt * 32 + i
-    const int key = kt * 32 + j;
-    if (key < N) {
-      unsigned w = 0u;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) w |= ((words[kt][i] >> j) & 1u) << i;
-      wk[(bh * N + key) * nkt + qt] = w;
-    }
-  }
-}
-
-// Shape, scale and grid checks of every entry point: blockIdx.y is the (sample, head) index, and the
-// forward takes the row max of the unscaled scores (a scale <= 0 would turn it into the row min).
-bool attn_ok(int B, int H, int N, int D, float scale) {
-  return B > 0 && H > 0 && N > 0 && N <= MAX_KT * 32 && D == HD && (long long)B * H <= 65535 &&
-         scale > 0.f && scale < INFINITY;  // (false for NaN)
-}
+static_assert(MAX_N_SHORT == 10 * 32, "ATTN_SWITCH instantiates 1 .. 10 tiles of 32");
 }  // namespace
 
+// (the keep words wq / wk come from triad_attn_dropmask, attention_mask.hip)
 extern "C" {
-
-int triad_attn_dropmask(int B, int H, int N, float p, unsigned seed, unsigned* wq, unsigned* wk, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || N <= 0 || N > MAX_KT * 32 || p < 0.f || p >= 1.f || (long long)B * H > 65535)
-    return TRIAD_EINVAL;
-  const int nkt = (N + 31) / 32;
-  hipLaunchKernelGGL(attn_dropmask_kernel, dim3(nkt, B * H), dim3(256), 0, stream, N, nkt, seed,
-                     triad_drop_thr(p), wq, wk);
-  TRIAD_CHECK_LAUNCH();
-  return TRIAD_OK;
-}
 
 int triad_attn_fwd_dropout(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
                            long long k_sN, const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D,
                            float scale, const unsigned* wq, float p, void* out, long long out_sB, long long out_sN,
                            float* lse, hipStream_t stream) {
-  if (!attn_ok(B, H, N, D, scale) || !(p >= 0.f && p < 1.f) || !lse) return TRIAD_EINVAL;
-  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(out, out_sB, out_sN))
-    return TRIAD_EINVAL;
   AttnArgs a = {};
-  a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
-  a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
-  a.v = (const bf16*)v; a.v_sB = v_sB; a.v_sN = v_sN;
-  a.out = (bf16*)out; a.out_sB = out_sB; a.out_sN = out_sN;
-  a.lse = lse; a.B = B; a.H = H; a.N = N; a.scale = scale;
+  if (!attn_fwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, B, H, N, D, scale, wq, p,
+                     {out, out_sB, out_sN}, lse))
+    return TRIAD_EINVAL;
   const int nt = (N + 31) / 32;
-  a.wq = wq; a.nkt = nt; a.drop_scale = 1.f / (1.f - p);
-  const dim3 grid((nt + 3) / 4, B * H);
+  const dim3 grid = attn_grid(B, H, N);
   if (wq) { ATTN_SWITCH(attn_fwd_kernel, true, nt, grid, a) }
   else { ATTN_SWITCH(attn_fwd_kernel, false, nt, grid, a) }
   TRIAD_CHECK_LAUNCH();
@@ -424,24 +343,13 @@ int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            const unsigned* wk, float p, void* dq, long long dq_sB, long long dq_sN, void* dk,
                            long long dk_sB, long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta,
                            hipStream_t stream) {
-  if (!attn_ok(B, H, N, D, scale) || !(p >= 0.f && p < 1.f) || (!wq != !wk) || !lse || !delta) return TRIAD_EINVAL;
-  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(o, o_sB, o_sN) ||
-      !row_ok(dout, do_sB, do_sN) || !row_ok(dq, dq_sB, dq_sN) || !row_ok(dk, dk_sB, dk_sN) ||
-      !row_ok(dv, dv_sB, dv_sN))
-    return TRIAD_EINVAL;
   AttnArgs a = {};
-  a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
-  a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
-  a.v = (const bf16*)v; a.v_sB = v_sB; a.v_sN = v_sN;
-  a.o = (const bf16*)o; a.o_sB = o_sB; a.o_sN = o_sN;
-  a.dout = (const bf16*)dout; a.do_sB = do_sB; a.do_sN = do_sN;
-  a.dq = (bf16*)dq; a.dq_sB = dq_sB; a.dq_sN = dq_sN;
-  a.dk = (bf16*)dk; a.dk_sB = dk_sB; a.dk_sN = dk_sN;
-  a.dv = (bf16*)dv; a.dv_sB = dv_sB; a.dv_sN = dv_sN;
-  a.lse = (float*)lse; a.delta = delta; a.B = B; a.H = H; a.N = N; a.scale = scale;
+  if (!attn_bwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, {o, o_sB, o_sN},
+                     {dout, do_sB, do_sN}, lse, B, H, N, D, scale, wq, wk, p, {dq, dq_sB, dq_sN}, {dk, dk_sB, dk_sN},
+                     {dv, dv_sB, dv_sN}, delta))
+    return TRIAD_EINVAL;
   const int nt = (N + 31) / 32;
-  a.wq = wq; a.wk = wk; a.nkt = nt; a.drop_scale = 1.f / (1.f - p);
-  const dim3 grid((nt + 3) / 4, B * H);
+  const dim3 grid = attn_grid(B, H, N);
   if (wq) {
     ATTN_SWITCH(attn_dq_kernel, true, nt, grid, a)
     ATTN_SWITCH(attn_dkv_kernel, true, nt, grid, a)

@@ -1,7 +1,8 @@
 // Backbone self-attention for sequences of 321 .. 2048 tokens (DINOv2-L/14 at 518 px: 1374 tokens,
 // HuBERT-large on 10 s of audio: 499; BASELINE configuration c5), forward and backward, bf16 in /
 // fp32 accumulate, head dim 64. Same tensor convention, MFMA orientation, swizzled LDS rows and
-// transposed reads as attention.hip (helpers in attention_tiles.h); what differs is that a
+// transposed reads as attention.hip (helpers, the argument struct AttnArgs and the entry points' checks
+// in attention_tiles.h; the keep words are written by attention_mask.hip); what differs is that a
 // (sample, head) sequence no longer fits in LDS, so the other side of each product is streamed in
 // chunks of KC = 64 rows through a two-slot LDS ring. Register-staged: the next chunk's global loads
 // are issued before the current chunk's MFMAs and written to the free slot after them, one barrier
@@ -28,25 +29,6 @@
 namespace {
 
 constexpr int KC = 64;             // rows per streamed chunk (two 32-row MFMA tiles)
-constexpr int MIN_N = 321;         // shorter sequences: attention.hip
-constexpr int MAX_N = 2048;
-constexpr int MAX_T32 = MAX_N / 32;
-
-struct LongArgs {
-  const bf16 *q, *k, *v, *o, *dout;
-  long long q_sB, q_sN, k_sB, k_sN, v_sB, v_sN, o_sB, o_sN, do_sB, do_sN;
-  bf16 *out, *dq, *dk, *dv;
-  long long out_sB, out_sN, dq_sB, dq_sN, dk_sB, dk_sN, dv_sB, dv_sN;
-  float* lse;       // [B*H][N] natural-log log-sum-exp of the scaled scores
-  float* delta;     // [B*H][N] rowsum(dO * O)
-  int B, H, N;
-  float scale;
-  const unsigned *wq, *wk;   // keep words (DROP kernels), wpr per row
-  int wpr;
-  float drop_scale;
-};
-
-__device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 
 // One chunk (KC rows x 64 dims) of two (b, h) slices in flight: 2 x 2 16-byte vectors per thread.
 struct Stage {
@@ -75,7 +57,7 @@ __device__ __forceinline__ void stage_store(const Stage& s, char* l0, char* l1) 
 
 // ---------------------------------------------------------------------------------------------
 template <bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(LongArgs a) {
+__global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2][2][KC * 128];   // [slot][K, V]
   const int bh = blockIdx.y, b = bh / a.H, hh = bh - b * a.H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, ql = lane & 31;
@@ -181,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(LongArgs a) {
 
 // dQ: wave = query tile, query on the lane, K / V chunks
 template <bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_long_dq_kernel(LongArgs a) {
+__global__ __launch_bounds__(256, 2) void attn_long_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2][2][KC * 128];   // [slot][K, V]
   const int bh = blockIdx.y, b = bh / a.H, hh = bh - b * a.H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, ql = lane & 31;
@@ -264,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_dq_kernel(LongArgs a) {
 
 // dK, dV: wave = key tile, key on the lane, Q / dO chunks with their lse log2e and delta
 template <bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_long_dkv_kernel(LongArgs a) {
+__global__ __launch_bounds__(256, 2) void attn_long_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2][2][KC * 128];   // [slot][Q, dO]
   __shared__ __attribute__((aligned(16))) float stat[2][2][KC];       // [slot][lse log2e, delta]
   const int bh = blockIdx.y, b = bh / a.H, hh = bh - b * a.H;
@@ -383,90 +365,20 @@ __global__ __launch_bounds__(256, 2) void attn_long_dkv_kernel(LongArgs a) {
   }
 }
 
-// Keep words in both layouts, wpr words per row (attention.hip's attn_dropmask_kernel with the row
-// padded to whole chunks). Block = the 32-query band qt of one (sample, head), all key tiles: thread
-// (row r, key tile kt) hashes its 16 element pairs into the wq word, the band's words meet in LDS and
-// thread (key row j, key tile kt) gathers bit j of the 32 words of tile kt into the wk word of key
-// 32 kt + j. Words of tiles that start at or past N are written as zero in both layouts.
-__global__ __launch_bounds__(256) void attn_long_dropmask_kernel(int N, int nt, int wpr, unsigned seed, unsigned thr,
-                                                                 unsigned* __restrict__ wq, unsigned* __restrict__ wk) {
-  __shared__ unsigned words[MAX_T32][33];
-  const int qt = blockIdx.x;
-  const long long bh = blockIdx.y;
-  for (int t = threadIdx.x; t < 32 * wpr; t += 256) {
-    const int r = t & 31, kt = t >> 5, q = qt * 32 + r;
-    unsigned bits = 0u;
-    if (q < N) {
-      const int ncol = min(32, N - kt * 32);
-      if (ncol > 0) {
-        const unsigned long long e0 = (unsigned long long)((bh * N + q) * N + kt * 32);
-        // pairs covering elements e0 .. e0 + ncol - 1
-        const unsigned long long p0 = e0 >> 1;
-        const int off = (int)(e0 & 1);
-        unsigned long long stream = 0ull;  // bit i = element e0 - off + i
-        const int npairs = (ncol + off + 1) >> 1;
-#pragma unroll
-        for (int i = 0; i < 17; ++i)  // constant shifts (npairs <= 17)
-          if (i < npairs) stream |= (unsigned long long)keep_pair(p0 + i, seed, thr) << (2 * i);
-        bits = (unsigned)(stream >> off);
-        if (ncol < 32) bits &= (1u << ncol) - 1u;
-      }
-      wq[(bh * N + q) * wpr + kt] = bits;
-    }
-    if (kt < nt) words[kt][r] = bits;
-  }
-  __syncthreads();
-  for (int t = threadIdx.x; t < 32 * nt; t += 256) {
-    const int j = t & 31, kt = t >> 5;  // key row kt * 32 + j: bit i = query qt * 32 + i
-    const int key = kt * 32 + j;
-    if (key < N) {
-      unsigned w = 0u;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) w |= ((words[kt][i] >> j) & 1u) << i;
-      wk[(bh * N + key) * wpr + qt] = w;
-      if (qt == nt - 1 && wpr > nt) wk[(bh * N + key) * wpr + nt] = 0u;   // the padding word of an odd tile count
-    }
-  }
-}
-
-bool long_ok(int B, int H, int N, int D, float scale, float p) {
-  return B > 0 && H > 0 && N >= MIN_N && N <= MAX_N && D == HD && (long long)B * H <= 65535 && scale > 0.f &&
-         scale < INFINITY && p >= 0.f && p < 1.f;  // (false for NaN)
-}
-// keep words are read two at a time
-bool words_ok(const unsigned* w) { return !((uintptr_t)w & 7); }
-
 }  // namespace
 
+// (the keep words wq / wk come from triad_attn_long_dropmask, attention_mask.hip)
 extern "C" {
-
-int triad_attn_long_dropmask(int B, int H, int N, float p, unsigned seed, unsigned* wq, unsigned* wk,
-                             hipStream_t stream) {
-  if (B <= 0 || H <= 0 || N < MIN_N || N > MAX_N || !(p >= 0.f && p < 1.f) || (long long)B * H > 65535 || !wq ||
-      !wk || !words_ok(wq) || !words_ok(wk))
-    return TRIAD_EINVAL;
-  const int nt = (N + 31) / 32, wpr = 2 * ((N + KC - 1) / KC);
-  hipLaunchKernelGGL(attn_long_dropmask_kernel, dim3(nt, B * H), dim3(256), 0, stream, N, nt, wpr, seed,
-                     triad_drop_thr(p), wq, wk);
-  TRIAD_CHECK_LAUNCH();
-  return TRIAD_OK;
-}
 
 int triad_attn_long_fwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
                         const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D, float scale,
                         const unsigned* wq, float p, void* out, long long out_sB, long long out_sN, float* lse,
                         hipStream_t stream) {
-  if (!long_ok(B, H, N, D, scale, p) || !lse || !words_ok(wq)) return TRIAD_EINVAL;
-  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(out, out_sB, out_sN))
+  AttnArgs a = {};
+  if (!attn_fwd_args(a, ATTN_LONG, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, B, H, N, D, scale, wq, p,
+                     {out, out_sB, out_sN}, lse))
     return TRIAD_EINVAL;
-  LongArgs a = {};
-  a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
-  a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
-  a.v = (const bf16*)v; a.v_sB = v_sB; a.v_sN = v_sN;
-  a.out = (bf16*)out; a.out_sB = out_sB; a.out_sN = out_sN;
-  a.lse = lse; a.B = B; a.H = H; a.N = N; a.scale = scale;
-  a.wq = wq; a.wpr = 2 * ((N + KC - 1) / KC); a.drop_scale = 1.f / (1.f - p);
-  const dim3 grid(((N + 31) / 32 + 3) / 4, B * H);
+  const dim3 grid = attn_grid(B, H, N);
   if (wq) hipLaunchKernelGGL(attn_long_fwd_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(attn_long_fwd_kernel<false>, grid, dim3(256), 0, stream, a);
   TRIAD_CHECK_LAUNCH();
@@ -479,24 +391,12 @@ int triad_attn_long_bwd(const void* q, long long q_sB, long long q_sN, const voi
                         int D, float scale, const unsigned* wq, const unsigned* wk, float p, void* dq, long long dq_sB,
                         long long dq_sN, void* dk, long long dk_sB, long long dk_sN, void* dv, long long dv_sB,
                         long long dv_sN, float* delta, hipStream_t stream) {
-  if (!long_ok(B, H, N, D, scale, p) || (!wq != !wk) || !words_ok(wq) || !words_ok(wk) || !lse || !delta)
+  AttnArgs a = {};
+  if (!attn_bwd_args(a, ATTN_LONG, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, {o, o_sB, o_sN},
+                     {dout, do_sB, do_sN}, lse, B, H, N, D, scale, wq, wk, p, {dq, dq_sB, dq_sN}, {dk, dk_sB, dk_sN},
+                     {dv, dv_sB, dv_sN}, delta))
     return TRIAD_EINVAL;
-  if (!row_ok(q, q_sB, q_sN) || !row_ok(k, k_sB, k_sN) || !row_ok(v, v_sB, v_sN) || !row_ok(o, o_sB, o_sN) ||
-      !row_ok(dout, do_sB, do_sN) || !row_ok(dq, dq_sB, dq_sN) || !row_ok(dk, dk_sB, dk_sN) ||
-      !row_ok(dv, dv_sB, dv_sN))
-    return TRIAD_EINVAL;
-  LongArgs a = {};
-  a.q = (const bf16*)q; a.q_sB = q_sB; a.q_sN = q_sN;
-  a.k = (const bf16*)k; a.k_sB = k_sB; a.k_sN = k_sN;
-  a.v = (const bf16*)v; a.v_sB = v_sB; a.v_sN = v_sN;
-  a.o = (const bf16*)o; a.o_sB = o_sB; a.o_sN = o_sN;
-  a.dout = (const bf16*)dout; a.do_sB = do_sB; a.do_sN = do_sN;
-  a.dq = (bf16*)dq; a.dq_sB = dq_sB; a.dq_sN = dq_sN;
-  a.dk = (bf16*)dk; a.dk_sB = dk_sB; a.dk_sN = dk_sN;
-  a.dv = (bf16*)dv; a.dv_sB = dv_sB; a.dv_sN = dv_sN;
-  a.lse = (float*)lse; a.delta = delta; a.B = B; a.H = H; a.N = N; a.scale = scale;
-  a.wq = wq; a.wk = wk; a.wpr = 2 * ((N + KC - 1) / KC); a.drop_scale = 1.f / (1.f - p);
-  const dim3 grid(((N + 31) / 32 + 3) / 4, B * H);
+  const dim3 grid = attn_grid(B, H, N);
   if (wq) {
     hipLaunchKernelGGL(attn_long_dq_kernel<true>, grid, dim3(256), 0, stream, a);
     hipLaunchKernelGGL(attn_long_dkv_kernel<true>, grid, dim3(256), 0, stream, a);

@@ -1,7 +1,9 @@
-// Tile helpers shared by the attention kernels (attention.hip: N <= 320, whole sequence in LDS;
-// attention_long.hip: 321 <= N <= 2048, K / V or Q / dO streamed in chunks): the swizzled LDS rows,
-// the row and transposed fragment reads, the accumulator-order packs and stores, and the tensor
-// check of the C ABI. See the header comment of attention.hip for the layouts.
+// What the attention translation units share (attention.hip: N <= 320, whole sequence in LDS;
+// attention_long.hip: 321 <= N <= 2048, K / V or Q / dO streamed in chunks; attention_mask.hip: the
+// dropout keep words of both). Device side: the swizzled LDS rows, the row and transposed fragment
+// reads, the accumulator-order packs and stores. Host side: the kernels' argument struct and the one
+// copy of every check and field assignment of the C ABI (attn_fwd_args, attn_bwd_args, attn_mask_ok).
+// See the header comment of attention.hip for the layouts.
 #pragma once
 #include "common.h"
 
@@ -10,8 +12,9 @@ namespace {
 constexpr int HD = 64;            // head dim
 constexpr float LOG2E = 1.4426950408889634f;
 
-// bit of accumulator element v (row / column (v & 3) + 8 (v >> 2) + 4 h of a 32-wide tile)
-__device__ __forceinline__ bool tile_bit(unsigned w, int v, int h) { return (w >> ((v & 3) + 8 * (v >> 2) + 4 * h)) & 1u; }
+// row / column of accumulator element v in a 32-wide tile (h = lane >> 5), and its bit of a keep word
+__device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
+__device__ __forceinline__ bool tile_bit(unsigned w, int v, int h) { return (w >> acc_row(v, h)) & 1u; }
 
 __device__ __forceinline__ int swz(int row) {
   const int k = (row >> 1) & 7;
@@ -61,8 +64,86 @@ __device__ __forceinline__ void store_cols(bf16* dst, const f32x16& a, float mul
   }
 }
 
+// ---- host side: the argument struct and the C ABI's checks, written once for both families -----------
+
+constexpr int MAX_N_SHORT = 320;   // whole-sequence kernels (attention.hip): 1 .. 320 tokens
+constexpr int MAX_N_LONG = 2048;   // streaming kernels (attention_long.hip): 321 .. 2048
+
+struct AttnArgs {
+  const bf16 *q, *k, *v, *o, *dout;
+  long long q_sB, q_sN, k_sB, k_sN, v_sB, v_sN, o_sB, o_sN, do_sB, do_sN;
+  bf16 *out, *dq, *dk, *dv;
+  long long out_sB, out_sN, dq_sB, dq_sN, dk_sB, dk_sN, dv_sB, dv_sN;
+  float* lse;       // [B*H][N] natural-log log-sum-exp of the scaled scores
+  float* delta;     // [B*H][N] rowsum(dO * O)
+  int B, H, N;
+  float scale;
+  // dropout on the attention probabilities (DROP kernels): keep bits by query row
+  // wq[(bh * N + q) * wpr + kt] (bit j = key 32 kt + j) and by key row wk[(bh * N + key) * wpr + qt]
+  // (bit j = query 32 qt + j); kept probabilities scaled by drop_scale = 1 / (1 - p)
+  const unsigned *wq, *wk;
+  int wpr;          // words per mask row (attn_wpr)
+  float drop_scale;
+};
+
+// The two kernel families as the checks see them: the token range, and whether a lane reads the two
+// keep words of a 64-row chunk as one 8-byte load (rows padded to whole chunks, 8-byte aligned masks).
+struct AttnFamily {
+  int nmin, nmax;
+  bool word_pairs;
+};
+constexpr AttnFamily ATTN_SHORT = {1, MAX_N_SHORT, false}, ATTN_LONG = {MAX_N_SHORT + 1, MAX_N_LONG, true};
+
+inline int attn_wpr(const AttnFamily& f, int N) { return f.word_pairs ? 2 * ((N + 63) / 64) : (N + 31) / 32; }
+// query (dq, forward) or key (dkv) tiles of 32, four per workgroup; blockIdx.y = (sample, head)
+inline dim3 attn_grid(int B, int H, int N) { return dim3(((N + 31) / 32 + 3) / 4, B * H); }
+
 // One tensor of the ABI: non-null, 16-byte aligned, strides in whole bf16x8 vectors (the kernels read
 // and write rows with 16- and 8-byte accesses at base + b sB + n sN + 64 h + 8 c).
-inline bool row_ok(const void* p, long long sB, long long sN) { return p && !((uintptr_t)p & 15) && !(sB % 8) && !(sN % 8); }
+struct AttnRows {
+  const void* p;
+  long long sB, sN;
+};
+template <class P>
+inline bool attn_rows(const AttnRows& r, P& p, long long& sB, long long& sN) {
+  p = (P)r.p; sB = r.sB; sN = r.sN;
+  return r.p && !((uintptr_t)r.p & 15) && !(r.sB % 8) && !(r.sN % 8);
+}
+
+// Sizes and mask pointers of every entry point: blockIdx.y is the (sample, head) index (<= 65535);
+// p in [0, 1) (the comparisons are false for NaN, which triad_drop_thr must never see).
+inline bool attn_mask_ok(const AttnFamily& f, int B, int H, int N, float p, const unsigned* wq, const unsigned* wk) {
+  const bool aligned = !f.word_pairs || !(((uintptr_t)wq | (uintptr_t)wk) & 7);
+  return B > 0 && H > 0 && N >= f.nmin && N <= f.nmax && (long long)B * H <= 65535 && p >= 0.f && p < 1.f && aligned;
+}
+
+// Checks and fields the forward and the backward share. The forward takes the row max of the unscaled
+// scores (a scale <= 0 would turn it into the row min), so the scale is finite and > 0 (false for NaN).
+inline bool attn_qkv_args(AttnArgs& a, const AttnFamily& f, AttnRows q, AttnRows k, AttnRows v, int B, int H, int N,
+                          int D, float scale, const unsigned* wq, const unsigned* wk, float p, const float* lse) {
+  if (!attn_mask_ok(f, B, H, N, p, wq, wk) || D != HD || !(scale > 0.f && scale < INFINITY) || !lse) return false;
+  a.lse = (float*)lse; a.B = B; a.H = H; a.N = N; a.scale = scale;
+  a.wq = wq; a.wk = wk; a.wpr = attn_wpr(f, N); a.drop_scale = 1.f / (1.f - p);
+  return attn_rows(q, a.q, a.q_sB, a.q_sN) && attn_rows(k, a.k, a.k_sB, a.k_sN) && attn_rows(v, a.v, a.v_sB, a.v_sN);
+}
+
+// Validate a forward / backward call of family f and fill the kernels' arguments; false = TRIAD_EINVAL
+// (a is then partly written and must not be launched).
+inline bool attn_fwd_args(AttnArgs& a, const AttnFamily& f, AttnRows q, AttnRows k, AttnRows v, int B, int H, int N,
+                          int D, float scale, const unsigned* wq, float p, AttnRows out, float* lse) {
+  return attn_qkv_args(a, f, q, k, v, B, H, N, D, scale, wq, nullptr, p, lse) &&
+         attn_rows(out, a.out, a.out_sB, a.out_sN);
+}
+
+inline bool attn_bwd_args(AttnArgs& a, const AttnFamily& f, AttnRows q, AttnRows k, AttnRows v, AttnRows o,
+                          AttnRows dout, const float* lse, int B, int H, int N, int D, float scale,
+                          const unsigned* wq, const unsigned* wk, float p, AttnRows dq, AttnRows dk, AttnRows dv,
+                          float* delta) {
+  a.delta = delta;
+  return attn_qkv_args(a, f, q, k, v, B, H, N, D, scale, wq, wk, p, lse) && (!wq == !wk) && delta &&
+         attn_rows(o, a.o, a.o_sB, a.o_sN) && attn_rows(dout, a.dout, a.do_sB, a.do_sN) &&
+         attn_rows(dq, a.dq, a.dq_sB, a.dq_sN) && attn_rows(dk, a.dk, a.dk_sB, a.dk_sN) &&
+         attn_rows(dv, a.dv, a.dv_sB, a.dv_sN);
+}
 
 }  // namespace

@@ -140,8 +140,7 @@ class Attention(nn.Module):
         B, N, C = x.shape
         qkv = self.qkv(x)
         d = C // self.heads
-        if attention.supported(qkv, N, d) or \
-                attention.supported_long(qkv, N, d, None, B * self.heads):  # HIP kernels (triad_amd.attention)
+        if attention.takes(qkv, B, self.heads, N, d):  # HIP kernels (triad_amd.attention)
             return self.proj(attention.attention_qkv(qkv, self.heads))
         qkv = qkv.reshape(B, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2])
