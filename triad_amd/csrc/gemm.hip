@@ -309,29 +309,17 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(const bf16* __restrict
 }
 
 // ---- 256 x 256 tile: LDS images and staging (the eight-wave form below) -------------------------
-// Tile 256 x 256 x 64 per stage, two 64 KB LDS slots, the next stage's DMA pieces issued in the
-// first half of the current one, vmcnt(0) + barrier at the top of the next. (Round 1 ran this tile
-// on four waves, 128 x 128 each; measured bounds, profiles/r01_gemm_w4_bounds.log: without the
-// fragment reads 3 % faster, without the DMA 25 % faster -- the LDS-DMA fill rate (~64 KB per CU per
-// stage) holds it under the MFMA rate. The eight-wave form replaced it in round 2, 3-13 % faster;
-// the four-wave kernel was deleted in round 5.)
+// Tile 256 x 256 x 64 per stage, two 64 KB LDS slots. Images (one wave-instruction = 1 KB):
+//   k-contiguous X ([rows][k]): [256][64], piece inst = rows 8 inst .. + 7 x 128 B, 16-byte chunk c
+//     of row m fetched into chunk c ^ ((m >> 1) & 7) (kc_off);
+//   X stored [k][rows]: two [64][128] halves, piece inst = half inst >> 4, k-rows 4 (inst & 15) .. + 3
+//     x 256 B, chunk c of row k fetched into chunk c ^ ((k & 3) << 2) (nc_off).
+// (Round 1 ran this tile on four waves, 128 x 128 each; measured bounds,
+// profiles/r01_gemm_w4_bounds.log: without the fragment reads 3 % faster, without the DMA 25 %
+// faster -- the LDS-DMA fill rate (~64 KB per CU per stage) holds it under the MFMA rate. The
+// eight-wave form replaced it in round 2, 3-13 % faster; the four-wave kernel was deleted in round 5.)
 constexpr int GW_M = 256, GW_N = 256;
 constexpr int GW_A = GW_M * BK, GW_ST = GW_A + GW_N * BK;  // elements per stage (64 KB)
-
-template <bool KCONTIG>
-__device__ __forceinline__ void gw_piece_one(const bf16* __restrict__ X, long long ld, int r0, int k0, bf16* img,
-                                             int inst, int lane) {
-  if (KCONTIG) {  // image [256][64]: 8 rows x 128 B per wave-instruction
-    const int m = inst * 8 + (lane >> 3), cp = lane & 7;
-    const int c = cp ^ ((m >> 1) & 7);
-    glds16(X + (size_t)(r0 + m) * ld + k0 + c * 8, img + inst * 512);
-  } else {  // X stored [k][rows]: two [64][128] halves, 4 k-rows x 256 B per wave-instruction
-    const int half = inst >> 4, ii = inst & 15;
-    const int k = ii * 4 + (lane >> 4), cp = lane & 15;
-    const int c = cp ^ ((k & 3) << 2);
-    glds16(X + (size_t)(k0 + k) * ld + r0 + half * 128 + c * 8, img + half * (BK * 128) + ii * 512);
-  }
-}
 
 template <bool KCONTIG>
 __device__ __forceinline__ bf16x8 gw_frag(const bf16* img, int row, int s, int lane) {
@@ -340,27 +328,202 @@ __device__ __forceinline__ bf16x8 gw_frag(const bf16* img, int row, int s, int l
 }
 
 // ---- 256 x 256 eight-wave form -----------------------------------------------------------------
-// The 256 x 256 tile, LDS images and staging with 8 waves (two per SIMD: one wave's DMA
-// issue and barrier waits overlap the other's MFMAs): wave (wm, wn) of 2 x 4 owns 128 x 64 (4 x 2
-// tiles of 32 x 32, 128 accumulators per lane), reads 6 fragments per 8 MFMAs per 16-deep step, and
-// issues 8 of the next stage's 64 DMA pieces (one after every 2nd of its first 16 MFMAs).
-constexpr int GE_PIECES = 8;
-// Measured and not kept (tools/build_variants.py + variant_ab.py, profiles/r02_gemm_w8_variants_ab.log,
-// 16 c3 shapes): s_setprio(1) around each step's MFMA cluster -0.4 %, a static priority for the
-// younger four waves 0.0 %, the next stage's 8 DMA pieces in a burst after the barrier +3.9 %;
-// transposed accumulators (B fragment first) with 8-byte row-run epilogue stores +10 %
-// (profiles/r02_gemm_w8_tepi_ab.log); the bf16 tile staged through LDS and stored as 128-B row runs
-// of 16-B stores: equal (profiles/r02_gemm_w8_ldsepi_ab.log). A diagnostic build without the
-// epilogue stores ran 10 % faster (18 % on the wide K = 768 shapes, profiles/
-// r02_gemm_w8_nostore_diag.log): the cost is the output write itself, ~128 KB per workgroup
-// issued by every CU of a dispatch round at once and not overlapped with any MFMA work.
+// The 256 x 256 tile with 8 waves, two per SIMD: wave (wm, wn) of 2 x 4 owns 128 x 64 (4 x 2 tiles
+// of 32 x 32, 128 accumulators per lane) and issues 8 of a stage's 64 DMA pieces. Until the
+// pipelined loop below, every stage began with vmcnt(0) + __syncthreads() (no DMA in flight across
+// a barrier, all eight waves in phase); measured in that drained structure and not kept
+// (profiles/r02_gemm_w8_variants_ab.log, 16 c3 shapes): s_setprio(1) around each step's MFMA
+// cluster -0.4 %, a static priority for the younger four waves 0.0 %, the next stage's 8 DMA
+// pieces in a burst after the barrier +3.9 %, a 4-slot ring of 32-deep chunks +5-8 %.
+// Measured in the pipelined structure (tools/gemm_w8_ab.py against the drained loop's build,
+// alternated in one process, profiles/gemm_w8_pipe_ab.log; every output bit-equal): the c3 shapes
+// weighted by launches -8.1 % (both operands k-contiguous), -7.4 % (input gradients), -12.7 %
+// (split-K weight gradients); 3-9 % at K = 768 (12 k-steps), 10-19 % from K = 2304 up. With every
+// wave executing the last k-step's trailing barrier and wm = 0 one more (wm = 0 then waits out
+// wm = 1's last MFMA cluster before its epilogue) the same sums read -6 / -7 / -10 % and the
+// two 8-k-step conv shapes were 10-12 % slower than the drained loop. s_setprio around the MFMA
+// clusters is kept as the structure needs it (without the pair hipcc moves MFMAs across the raw
+// barriers); it was not measured apart in this structure.
+// Epilogue forms measured on the drained loop and not kept: transposed accumulators (B fragment
+// first) with 8-byte row-run stores +10 % (profiles/r02_gemm_w8_tepi_ab.log); the bf16 tile staged
+// through LDS and stored as 128-B row runs of 16-B stores: equal
+// (profiles/r02_gemm_w8_ldsepi_ab.log). A diagnostic build without the epilogue stores ran 10 %
+// faster (18 % on the wide K = 768 shapes, profiles/r02_gemm_w8_nostore_diag.log): the cost is the
+// output write itself, ~128 KB per workgroup issued by every CU of a dispatch round at once and not
+// overlapped with any MFMA work.
 
-template <bool A_KCONTIG, bool B_KCONTIG>
-__device__ __forceinline__ void ge_piece(const bf16* __restrict__ A, long long lda, const bf16* __restrict__ B,
-                                         long long ldb, int m0, int n0, int k0, bf16* dst, int wave, int lane,
-                                         int u) {
-  if (u < 4) gw_piece_one<A_KCONTIG>(A, lda, m0, k0, dst, wave * 4 + u, lane);
-  else gw_piece_one<B_KCONTIG>(B, ldb, n0, k0, dst + GW_A, wave * 4 + (u - 4), lane);
+// ---- the pipelined main loop: LDS-DMA in flight across raw barriers ------------------------------
+// One k-step (a 64-deep stage in slot c = kt & 1) is four phases; phase p is this wave's 8 MFMAs
+// on one 64 x 32 quadrant of its 128 x 64 output over the whole stage:
+//     fragment reads | one half-tile's 2 DMA pieces | [vmcnt] | lgkmcnt(0) | s_barrier |
+//     s_setprio(1), 8 MFMAs, s_setprio(0) | s_barrier
+// Quadrants and the fragments a phase reads (kept in registers until their last quadrant):
+//     p0: (rows 0-63, cols 0-31)   reads A rows 0-63, B cols 0-31 (and cols 32-63 when B is [k][n])
+//     p1: (rows 0-63, cols 32-63)  reads B cols 32-63 (B [n][k] only)
+//     p2: (rows 64-127, cols 32-63) reads A rows 64-127
+//     p3: (rows 64-127, cols 0-31)  reads nothing
+// A stage is four half-tiles of 16 KB = GP_LOADS (2) wave-instructions per wave each. A: pieces
+// wave * 4 + u, u in {0, 1} / {2, 3}. B [k][n]: the same. B [n][k]: half hh is the 32-column
+// sub-tiles hh of all four wave columns (n = 64 wn + 32 hh + 0..31), so that half 0 is read in p0
+// only. Issue order, global phase P = 4 kt + p (stage kt + 1 lives in slot c ^ 1, kt + 2 in c):
+//     p0: A half 1 of stage kt + 1      p1: B half 0 of stage kt + 2
+//     p2: B half 1 of stage kt + 2      p3: A half 0 of stage kt + 2, then vmcnt(GP_LOADS * GP_FLIGHT)
+// Wave rows wm = 1 run one barrier behind wm = 0 (one s_barrier more before their first phase, one
+// fewer after their last MFMA cluster: every wave executes 1 + 8 nk barriers), so on every SIMD one
+// wave's MFMA cluster runs beside the other's reads and DMA issue. Number the barriers every wave
+// executes g = 0, 1, ...: wm = 0 runs the read / issue / wait part of phase P before barrier 2P and
+// its MFMAs before 2P + 1; wm = 1 before 2P + 1 and 2P + 2.
+//   RAW (LDS-DMA data is ordered for a ds_read only by the issuing wave's vmcnt and a barrier the
+//   reader has passed since): p3's vmcnt(6) leaves the three half-tiles issued in p1-p3 (stage
+//   kt + 2) in flight and retires everything older, i.e. all of stage kt + 1, in every wave before
+//   barrier 2(4 kt + 3) + 1 at the latest (wm = 1). Stage kt + 1 is first read in phase 4 kt + 4:
+//   before barrier 2(4 kt + 4) by wm = 0 and a barrier later by wm = 1 -- after that barrier for
+//   both. Never in the phase of the wait itself.
+//   WAR (a slot half may be restaged one phase after its last read, because every phase retires
+//   its reads with lgkmcnt(0) BEFORE its first barrier: reads of phase P are done in every wave at
+//   barrier 2P + 1, and the earliest issue of phase P + 1 is wm = 0's, after barrier 2P + 1):
+//     B half 0 of slot c: last read p0 (phase 4 kt)      restaged 4 kt + 1
+//     B half 1 of slot c: last read p1 (p0 for [k][n])   restaged 4 kt + 2
+//     A (both halves) of slot c: last read p2            restaged 4 kt + 3 (half 0), 4 kt + 4 (half 1)
+// Prologue: stage 0 and the first three half-tiles of stage 1, vmcnt(6) (vmcnt(0) when nk = 1),
+// barrier. The loop body is two steady k-steps (static slots) and runs while three stages remain;
+// the last two k-steps run after it: the one before last issues only A half 1 of the last stage
+// and drains with vmcnt(0) in its p3, the last issues nothing, so no slot is read unstaged for any
+// nk >= 1. Inside the loop no wait is vmcnt(0). (tests/test_gemm_w8_isa_cpu.py re-derives the
+// constant from the emitted loop.)
+constexpr int GP_LOADS = 2;    // LDS-DMA wave-instructions per wave per half-tile
+constexpr int GP_FLIGHT = 3;   // half-tiles left in flight by the steady-state wait
+enum { GP_STEADY = 0, GP_PENULT = 1, GP_LAST = 2 };
+
+// One DMA piece of the images above, addressed as a wave-uniform 64-bit base (SGPRs) plus a
+// 32-bit per-lane byte offset: the per-lane part of a piece's source address depends only on the
+// lane and on the piece's parity (inst & 1 enters the k-contiguous swizzle), so a stage's 8 pieces
+// need 4 offset VGPRs in all instead of 8 per-lane 64-bit pointers. The base is computed on the
+// scalar unit; s_nop 2 keeps five wait states between any instruction before the statement and
+// the load should hipcc ever hand over a base fresh from v_readfirstlane (and covers M0 -> DMA).
+__device__ __forceinline__ void glds16_so(const void* sbase, unsigned voff, void* lds_base) {
+  const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)LDS_PTR(void, lds_base));
+  TRIAD_LDS_DMA_CHECK(lds, 1);
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 2\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds)
+      : "memory");
+}
+
+// per-lane byte offset of a piece of parity j: row lane >> 3 (k-row lane >> 4) and the swizzled chunk
+template <bool KCONTIG>
+__device__ __forceinline__ unsigned gp_voff(long long ld, int lane, int j) {
+  if (KCONTIG) {
+    const int mr = lane >> 3, c = (lane & 7) ^ (((j * 8 + mr) >> 1) & 7);
+    return (unsigned)((mr * ld + c * 8) * 2);
+  }
+  const int kr = lane >> 4, c = (lane & 15) ^ ((kr & 3) << 2);
+  return (unsigned)((kr * ld + c * 8) * 2);
+}
+
+template <bool KCONTIG>
+__device__ __forceinline__ void gp_piece(const bf16* __restrict__ X, long long ld, int r0, int k0, bf16* img, int inst,
+                                         unsigned voff) {
+  if (KCONTIG) {
+    glds16_so(X + (size_t)(r0 + inst * 8) * ld + k0, voff, img + inst * 512);
+  } else {
+    const int half = inst >> 4, ii = inst & 15;
+    glds16_so(X + (size_t)(k0 + ii * 4) * ld + r0 + half * 128, voff, img + half * (BK * 128) + ii * 512);
+  }
+}
+
+template <bool KCONTIG, bool SUBS>
+__device__ __forceinline__ void gp_half(const bf16* __restrict__ X, long long ld, int r0, int k0, bf16* img, int wave,
+                                        const unsigned (&voff)[2], int hh) {
+#pragma unroll
+  for (int j = 0; j < GP_LOADS; ++j) {
+    const int k = wave * 2 + j;
+    const int inst = SUBS ? (k >> 2) * 8 + hh * 4 + (k & 3) : wave * 4 + hh * 2 + j;   // inst & 1 == j
+    gp_piece<KCONTIG>(X, ld, r0, k0, img, inst, voff[j]);
+  }
+}
+
+// end of a phase's read / issue part: this wave's fragment reads retired, then the barrier
+__device__ __forceinline__ void gp_sync() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// the 8 MFMAs of quadrant (rows 64 ah .. + 63, cols 32 b .. + 31) over the four 16-deep steps
+__device__ __forceinline__ void gp_quadrant(f32x16 (&acc)[4][2], const bf16x8 (&af)[2][4], const bf16x8 (&bf)[4], int ah,
+                                            int b, bool trail = true) {
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int s = 0; s < BK / 16; ++s)
+#pragma unroll
+    for (int a = 0; a < 2; ++a) acc[2 * ah + a][b] = mfma32(af[a][s], bf[s], acc[2 * ah + a][b]);
+  __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_sched_barrier(0);
+  if (trail) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// k-step kt from slot `slot` (a constant in the loop); kn = the k offset of stage kt + 1
+template <bool A_KCONTIG, bool B_KCONTIG, int MODE>
+__device__ __forceinline__ void gp_step(const bf16* __restrict__ A, long long lda, const bf16* __restrict__ B,
+                                        long long ldb, int m0, int n0, int kn, bf16* lds, int slot, int wave, int lane,
+                                        int wm, int wn, const unsigned (&va)[2], const unsigned (&vb)[2],
+                                        f32x16 (&acc)[4][2]) {
+  bf16* const cur = lds + slot * GW_ST;
+  bf16* const oth = lds + (slot ^ 1) * GW_ST;
+  const bf16* ai = cur;
+  const bf16* bi = cur + GW_A;
+  bf16x8 af[2][4], bfr[2][4];
+  // p0
+#pragma unroll
+  for (int s = 0; s < 4; ++s) bfr[0][s] = gw_frag<B_KCONTIG>(bi, wn * 64, s, lane);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) af[a][s] = gw_frag<A_KCONTIG>(ai, wm * 128 + a * 32, s, lane);
+  if (!B_KCONTIG)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) bfr[1][s] = gw_frag<B_KCONTIG>(bi, wn * 64 + 32, s, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  if (MODE != GP_LAST) gp_half<A_KCONTIG, false>(A, lda, m0, kn, oth, wave, va, 1);
+  gp_sync();
+  gp_quadrant(acc, af, bfr[0], 0, 0);
+  // p1
+  if (B_KCONTIG)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) bfr[1][s] = gw_frag<B_KCONTIG>(bi, wn * 64 + 32, s, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kn + BK, cur + GW_A, wave, vb, 0);
+  gp_sync();
+  gp_quadrant(acc, af, bfr[1], 0, 1);
+  // p2
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) af[a][s] = gw_frag<A_KCONTIG>(ai, wm * 128 + 64 + a * 32, s, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kn + BK, cur + GW_A, wave, vb, 1);
+  gp_sync();
+  gp_quadrant(acc, af, bfr[1], 1, 1);
+  // p3
+  if (MODE == GP_STEADY) {
+    gp_half<A_KCONTIG, false>(A, lda, m0, kn + BK, cur, wave, va, 0);
+    TRIAD_VMCNT(GP_LOADS * GP_FLIGHT);
+  } else if (MODE == GP_PENULT) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  gp_sync();
+  // the last barrier of the last k-step: only wm = 0 executes it (it is wm = 1's barrier before
+  // these MFMAs), which evens out the one barrier wm = 1 ran more at the start
+  gp_quadrant(acc, af, bfr[0], 1, 0, MODE != GP_LAST || wm == 0);
 }
 
 template <bool A_KCONTIG, bool B_KCONTIG, typename OutT>
@@ -387,45 +550,44 @@ __global__ __launch_bounds__(512, 1) void gemm_w8_kernel(const bf16* __restrict_
   const int kbeg = split * k_per_split;
   const int nk = __builtin_amdgcn_readfirstlane(max(0, min(k_per_split, Kd - kbeg)) / BK);
   C += (size_t)split * slab_stride;
-  if (nk > 0)
+  if (nk > 0) {
+    const unsigned va[2] = {gp_voff<A_KCONTIG>(lda, lane, 0), gp_voff<A_KCONTIG>(lda, lane, 1)};
+    const unsigned vb[2] = {gp_voff<B_KCONTIG>(ldb, lane, 0), gp_voff<B_KCONTIG>(ldb, lane, 1)};
 #pragma unroll
-    for (int u = 0; u < GE_PIECES; ++u)
-      ge_piece<A_KCONTIG, B_KCONTIG>(A, lda, B, ldb, m0, n0, kbeg, lds, wave, lane, u);
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const bool pf = kt + 1 < nk;
-    bf16* const nb = lds + ((kt + 1) & 1) * GW_ST;
-    const int kn = kbeg + (kt + 1) * BK;
-    const bf16* ai = lds + (kt & 1) * GW_ST;
-    const bf16* bi = ai + GW_A;
-    bf16x8 af[2][4], bfr[2][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) af[0][t] = gw_frag<A_KCONTIG>(ai, wm * 128 + t * 32, 0, lane);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bfr[0][t] = gw_frag<B_KCONTIG>(bi, wn * 64 + t * 32, 0, lane);
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      const int cur = s & 1;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          acc[a][b] = mfma32(af[cur][a], bfr[cur][b], acc[a][b]);
-          const int j = a * 2 + b, mi = s * 8 + j;
-          if (s + 1 < BK / 16 && j < 6) {  // step s + 1's 6 fragments between step s's MFMAs
-            __builtin_amdgcn_sched_barrier(0);
-            if (j < 4) af[cur ^ 1][j] = gw_frag<A_KCONTIG>(ai, wm * 128 + j * 32, s + 1, lane);
-            else bfr[cur ^ 1][j - 4] = gw_frag<B_KCONTIG>(bi, wn * 64 + (j - 4) * 32, s + 1, lane);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if (mi % 2 == 1 && mi / 2 < GE_PIECES) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (pf) ge_piece<A_KCONTIG, B_KCONTIG>(A, lda, B, ldb, m0, n0, kn, nb, wave, lane, mi / 2);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
+    for (int hh = 0; hh < 2; ++hh) {
+      gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kbeg, lds + GW_A, wave, vb, hh);
+      gp_half<A_KCONTIG, false>(A, lda, m0, kbeg, lds, wave, va, hh);
     }
+    if (nk > 1) {
+      gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kbeg + BK, lds + GW_ST + GW_A, wave, vb, 0);
+      gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kbeg + BK, lds + GW_ST + GW_A, wave, vb, 1);
+      gp_half<A_KCONTIG, false>(A, lda, m0, kbeg + BK, lds + GW_ST, wave, va, 0);
+      TRIAD_VMCNT(GP_LOADS * GP_FLIGHT);
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    if (wm) __builtin_amdgcn_s_barrier();   // the stagger
+    __builtin_amdgcn_sched_barrier(0);
+#define GP_STEP(slot, MODE, kt)                                                                                \
+  gp_step<A_KCONTIG, B_KCONTIG, MODE>(A, lda, B, ldb, m0, n0, kbeg + ((kt) + 1) * BK, lds, slot, wave, lane, wm, wn, \
+                                      va, vb, acc)
+    int kt = 0;
+    for (; kt + 3 < nk; kt += 2) {
+      GP_STEP(0, GP_STEADY, kt);
+      GP_STEP(1, GP_STEADY, kt + 1);
+    }
+    // 1 (nk = 1 only), 2 or 3 k-steps are left and kt is even
+    if (nk - kt == 3) {
+      GP_STEP(0, GP_STEADY, kt);
+      ++kt;
+    }
+    if (nk - kt == 2) {
+      GP_STEP(kt & 1, GP_PENULT, kt);
+      ++kt;
+    }
+    GP_STEP(kt & 1, GP_LAST, kt);
+#undef GP_STEP
   }
 
   const float alpha = alpha_p ? *alpha_p : 1.f;
