@@ -255,6 +255,24 @@ int triad_gemm_bf16_form(const void* A, long long lda, int a_kcontig, const void
                          int M, int N, int Kd, const float* alpha, void* C, long long ldc, int out_bf16, int form,
                          hipStream_t stream);
 
+/* The 256 x 256 eight-wave form runs its output tiles one per workgroup, or, when the tiles exceed
+ * the CUs, several back to back in one workgroup (the multi-tile kernel: no pipeline drain, prologue
+ * or dispatch between a workgroup's tiles; bit-identical outputs). Every splits == 1 call that takes
+ * form 4 is routed by this rule: with R = ceil(tiles / cus), R == 1 -> 0 (one tile per workgroup),
+ * else ceil(tiles / R) workgroups, workgroup g running tiles g, g + workgroups, ...
+ * Host only, no device call. TRIAD_EINVAL for tiles <= 0 or cus <= 0. */
+int triad_gemm_w8_workgroups(int tiles, int cus);
+
+/* The multi-tile eight-wave kernel on a caller-chosen grid (tests and tools; the product entry points
+ * above route themselves): C = alpha * op(A) . op(B) (+ bias[n], fp32 or, bias_bf16 != 0, bf16; NULL
+ * for none), C fp32 or bf16. Every rule of the GEMM entry points above, and TRIAD_EINVAL unless
+ * M, N are multiples of 256, 1 <= workgroups <= (M / 256)(N / 256) and ldc <= 2^27 (a lane's
+ * store offset over 4 rows of C is a 32-bit register; the routed path keeps the one-tile kernel
+ * for a wider C). */
+int triad_gemm_bf16_tiles(const void* A, long long lda, int a_kcontig, const void* B, long long ldb, int b_kcontig,
+                          int M, int N, int Kd, const float* alpha, void* C, long long ldc, int out_bf16,
+                          const void* bias, int bias_bf16, int workgroups, hipStream_t stream);
+
 /* Projection head on row-panel GEMMs (model.py:32-34,68 / 81-83,116 / 253-255,326 under bf16
  * autocast; csrc/rowgemm.hip): a workgroup owns 128 token rows x all 512 columns, so the LayerNorm
  * and its backward run in the GEMM epilogues. Weights are pre-arranged in MFMA-fragment order:

@@ -78,6 +78,8 @@ SIGNATURES = {
     "triad_chgn_gelu_fwd": [vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp],
     "triad_chgn_gelu_bwd": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "triad_gemm_bf16_form": [vp, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, i64, i32, i32, vp],
+    "triad_gemm_w8_workgroups": [i32, i32],
+    "triad_gemm_bf16_tiles": [vp, i64, i32, vp, i64, i32, i32, i32, i32, vp, vp, i64, i32, vp, i32, i32, vp],
     "triad_conv0_dw_workspace_bytes": [i32, i32, i32],
     "triad_conv0_dw": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
     "triad_c0gn_fwd": [vp, i64, vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp],
@@ -124,7 +126,7 @@ RESTYPES = {"triad_pairsim_nparts": C.c_int, "triad_chgn_workspace_bytes": C.c_l
             "triad_posconv_dw_part_bytes": C.c_longlong,
             "triad_lora_tn_blocks": C.c_int, "triad_dropaddln_bwd_blocks": C.c_int,
             "triad_colsum_splits": C.c_int, "triad_colsum_dma_splits": C.c_int, "triad_dense_nparts": C.c_int,
-            "triad_rowpanel_count": C.c_int}
+            "triad_rowpanel_count": C.c_int, "triad_gemm_w8_workgroups": C.c_int}
 
 # Entry points that serve ONLY the backbones' layers (frontend.py, postln.py, vit.py, attention.py):
 # not part of the hot path. Every other launching entry point is hot-path work and is
@@ -133,7 +135,8 @@ RESTYPES = {"triad_pairsim_nparts": C.c_int, "triad_chgn_workspace_bytes": C.c_l
 # Shared entry points (the GEMMs, column and slab sums) are hot-path ones whose backbone launches
 # carry meta=dict(backbone=True) and are reported apart.
 BACKBONE_ENTRY_POINTS = frozenset({
-    "triad_chgn_gelu_fwd", "triad_chgn_gelu_bwd", "triad_gemm_bf16_form", "triad_conv0_dw", "triad_c0gn_fwd",
+    "triad_chgn_gelu_fwd", "triad_chgn_gelu_bwd", "triad_gemm_bf16_form", "triad_gemm_bf16_tiles", "triad_conv0_dw",
+    "triad_c0gn_fwd",
     "triad_posconv", "triad_posconv_dw", "triad_gemm_bf16_splitk", "triad_rows_nt", "triad_lora_update",
     "triad_dropaddln_fwd", "triad_dropaddln_bwd", "triad_gelu_table", "triad_geludrop_fwd", "triad_geludrop_bwd",
     "triad_dropout_keep", "triad_addln_fwd", "triad_addln_bwd", "triad_lora_tn", "triad_attn_dropmask",

@@ -13,6 +13,9 @@
 // the reads (ds_read_b128 for k-contiguous, ds_read_b64_tr_b16 for the others).
 #include "common.h"
 
+#include <atomic>
+#include <type_traits>
+
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
@@ -88,6 +91,11 @@ __device__ __forceinline__ float bias_at(const void* bias, int bias_bf16, int n)
 // token slab of both operands is fetched from HBM once, into that XCD's L2, and read from there
 // by all its tiles (the default mapping puts each split's tiles on all eight XCDs: each operand
 // slab is fetched up to 8 times). Placement is a speed matter only; results do not depend on it.
+__device__ __forceinline__ int xcd_tile(int bid, int T) {
+  const int q8 = T / 8, r8 = T % 8, x = bid % 8;
+  return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + bid / 8;
+}
+
 __device__ __forceinline__ void tile_split(int xsplit, int& tile, int& split) {
   const int T = gridDim.x;
   if (xsplit) {
@@ -96,8 +104,7 @@ __device__ __forceinline__ void tile_split(int xsplit, int& tile, int& split) {
     split = c + 8 * (i / T);
     return;
   }
-  const int bid = blockIdx.x, q8 = T / 8, r8 = T % 8, x = bid % 8;
-  tile = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + bid / 8;
+  tile = xcd_tile(blockIdx.x, T);
   split = blockIdx.y;
 }
 
@@ -416,6 +423,29 @@ __device__ __forceinline__ void glds16_so(const void* sbase, unsigned voff, void
       : "memory");
 }
 
+// The same with the destination as an LDS byte address in a scalar register (the multi-tile kernel:
+// `ptr + elements` of a bf16 image pointer written for addresses, so the staging code below serves
+// both). The multi-tile loop makes the base opaque once per k-step, so a piece's address is one
+// scalar add in the loop and not one of 32 loop-invariant registers the loop has no room for.
+struct GtLds {
+  unsigned addr;
+  __device__ __forceinline__ GtLds operator+(int elems) const { return GtLds{addr + 2u * (unsigned)elems}; }
+};
+
+__device__ __forceinline__ void glds16_so(const void* sbase, unsigned voff, GtLds dst) {
+  TRIAD_LDS_DMA_CHECK(dst.addr, 2);
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 2\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(dst.addr)
+      : "memory");
+}
+
 // per-lane byte offset of a piece of parity j: row lane >> 3 (k-row lane >> 4) and the swizzled chunk
 template <bool KCONTIG>
 __device__ __forceinline__ unsigned gp_voff(long long ld, int lane, int j) {
@@ -427,8 +457,8 @@ __device__ __forceinline__ unsigned gp_voff(long long ld, int lane, int j) {
   return (unsigned)((kr * ld + c * 8) * 2);
 }
 
-template <bool KCONTIG>
-__device__ __forceinline__ void gp_piece(const bf16* __restrict__ X, long long ld, int r0, int k0, bf16* img, int inst,
+template <bool KCONTIG, typename D>
+__device__ __forceinline__ void gp_piece(const bf16* __restrict__ X, long long ld, int r0, int k0, D img, int inst,
                                          unsigned voff) {
   if (KCONTIG) {
     glds16_so(X + (size_t)(r0 + inst * 8) * ld + k0, voff, img + inst * 512);
@@ -438,8 +468,8 @@ __device__ __forceinline__ void gp_piece(const bf16* __restrict__ X, long long l
   }
 }
 
-template <bool KCONTIG, bool SUBS>
-__device__ __forceinline__ void gp_half(const bf16* __restrict__ X, long long ld, int r0, int k0, bf16* img, int wave,
+template <bool KCONTIG, bool SUBS, typename D>
+__device__ __forceinline__ void gp_half(const bf16* __restrict__ X, long long ld, int r0, int k0, D img, int wave,
                                         const unsigned (&voff)[2], int hh) {
 #pragma unroll
   for (int j = 0; j < GP_LOADS; ++j) {
@@ -471,16 +501,23 @@ __device__ __forceinline__ void gp_quadrant(f32x16 (&acc)[4][2], const bf16x8 (&
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// k-step kt from slot `slot` (a constant in the loop); kn = the k offset of stage kt + 1
-template <bool A_KCONTIG, bool B_KCONTIG, int MODE>
-__device__ __forceinline__ void gp_step(const bf16* __restrict__ A, long long lda, const bf16* __restrict__ B,
-                                        long long ldb, int m0, int n0, int kn, bf16* lds, int slot, int wave, int lane,
-                                        int wm, int wn, const unsigned (&va)[2], const unsigned (&vb)[2],
-                                        f32x16 (&acc)[4][2]) {
-  bf16* const cur = lds + slot * GW_ST;
-  bf16* const oth = lds + (slot ^ 1) * GW_ST;
-  const bf16* ai = cur;
-  const bf16* bi = cur + GW_A;
+struct GpNoHook {};   // gp_step's p3_scalar of the one-tile kernel: nothing
+
+// The k-step of one stage from slot `slot` (a constant in the loop). A1 at (m1, k1) = the A rows
+// and k offset of the next stage, A2 / B2 at (m2, n2, k2) = the tile origin and k offset of the
+// stage after that: the one-tile kernel passes its operands and its own tile at kn and kn + BK,
+// the multi-tile kernel pointers to whatever tile those stages belong to (and zeros). dst = the
+// two slots as the LDS-DMA's destination: lds itself, or its address (GtLds).
+template <bool A_KCONTIG, bool B_KCONTIG, int MODE, typename D, typename H>
+__device__ __forceinline__ void gp_step(const bf16* __restrict__ A1, const bf16* __restrict__ A2, long long lda,
+                                        const bf16* __restrict__ B2, long long ldb, int m1, int k1, int m2, int n2,
+                                        int k2, bf16* lds, D dst, int slot, int wave, int lane, int wm, int wn,
+                                        const unsigned (&va)[2], const unsigned (&vb)[2], f32x16 (&acc)[4][2],
+                                        H p3_scalar) {
+  const D cur = dst + slot * GW_ST;
+  const D oth = dst + (slot ^ 1) * GW_ST;
+  const bf16* ai = lds + slot * GW_ST;
+  const bf16* bi = ai + GW_A;
   bf16x8 af[2][4], bfr[2][4];
   // p0
 #pragma unroll
@@ -493,7 +530,7 @@ __device__ __forceinline__ void gp_step(const bf16* __restrict__ A, long long ld
 #pragma unroll
     for (int s = 0; s < 4; ++s) bfr[1][s] = gw_frag<B_KCONTIG>(bi, wn * 64 + 32, s, lane);
   __builtin_amdgcn_sched_barrier(0);
-  if (MODE != GP_LAST) gp_half<A_KCONTIG, false>(A, lda, m0, kn, oth, wave, va, 1);
+  if (MODE != GP_LAST) gp_half<A_KCONTIG, false>(A1, lda, m1, k1, oth, wave, va, 1);
   gp_sync();
   gp_quadrant(acc, af, bfr[0], 0, 0);
   // p1
@@ -501,7 +538,7 @@ __device__ __forceinline__ void gp_step(const bf16* __restrict__ A, long long ld
 #pragma unroll
     for (int s = 0; s < 4; ++s) bfr[1][s] = gw_frag<B_KCONTIG>(bi, wn * 64 + 32, s, lane);
   __builtin_amdgcn_sched_barrier(0);
-  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kn + BK, cur + GW_A, wave, vb, 0);
+  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B2, ldb, n2, k2, cur + GW_A, wave, vb, 0);
   gp_sync();
   gp_quadrant(acc, af, bfr[1], 0, 1);
   // p2
@@ -510,12 +547,13 @@ __device__ __forceinline__ void gp_step(const bf16* __restrict__ A, long long ld
 #pragma unroll
     for (int s = 0; s < 4; ++s) af[a][s] = gw_frag<A_KCONTIG>(ai, wm * 128 + 64 + a * 32, s, lane);
   __builtin_amdgcn_sched_barrier(0);
-  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B, ldb, n0, kn + BK, cur + GW_A, wave, vb, 1);
+  if (MODE == GP_STEADY) gp_half<B_KCONTIG, B_KCONTIG>(B2, ldb, n2, k2, cur + GW_A, wave, vb, 1);
   gp_sync();
   gp_quadrant(acc, af, bfr[1], 1, 1);
-  // p3
+  // p3 (the phase with no fragment reads: the multi-tile kernel's scalar bookkeeping rides here)
+  if constexpr (!std::is_same<H, GpNoHook>::value) p3_scalar();
   if (MODE == GP_STEADY) {
-    gp_half<A_KCONTIG, false>(A, lda, m0, kn + BK, cur, wave, va, 0);
+    gp_half<A_KCONTIG, false>(A2, lda, m2, k2, cur, wave, va, 0);
     TRIAD_VMCNT(GP_LOADS * GP_FLIGHT);
   } else if (MODE == GP_PENULT) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -570,8 +608,8 @@ __global__ __launch_bounds__(512, 1) void gemm_w8_kernel(const bf16* __restrict_
     if (wm) __builtin_amdgcn_s_barrier();   // the stagger
     __builtin_amdgcn_sched_barrier(0);
 #define GP_STEP(slot, MODE, kt)                                                                                \
-  gp_step<A_KCONTIG, B_KCONTIG, MODE>(A, lda, B, ldb, m0, n0, kbeg + ((kt) + 1) * BK, lds, slot, wave, lane, wm, wn, \
-                                      va, vb, acc)
+  gp_step<A_KCONTIG, B_KCONTIG, MODE>(A, A, lda, B, ldb, m0, kbeg + ((kt) + 1) * BK, m0, n0, kbeg + ((kt) + 2) * BK, \
+                                      lds, lds, slot, wave, lane, wm, wn, va, vb, acc, GpNoHook{})
     int kt = 0;
     for (; kt + 3 < nk; kt += 2) {
       GP_STEP(0, GP_STEADY, kt);
@@ -605,6 +643,249 @@ __global__ __launch_bounds__(512, 1) void gemm_w8_kernel(const bf16* __restrict_
     }
 }
 
+// ---- the multi-tile form: one workgroup runs several 256 x 256 tiles back to back ----------------
+// Workgroup g of W = gridDim.x takes the tiles of linear index g, g + W, g + 2 W, ... (< tiles),
+// each mapped through tile_split's XCD remap with T = tiles, and runs the pipelined loop above over
+// the CONCATENATION of their k loops: number the workgroup's stages s = 0, 1, ... across all its
+// tiles, stage s = k-step s % nk of its (s / nk)-th tile, living in slot s & 1. The issue schedule
+// is the one-tile kernel's with kt read as s (p0: A half 1 of stage s + 1; p1-p3: B half 0, B half
+// 1, A half 0 of stage s + 2; vmcnt(GP_LOADS * GP_FLIGHT) in p3); only the source addresses differ:
+// the (m0, n0, k) of stages s + 1 and s + 2 are carried in scalar registers (GtCur) and may belong
+// to the next tile, or with nk = 1 to the tile after that. The RAW / WAR argument above speaks only
+// of stages, slots and phases, so it holds for the flattened sequence as written: p3's wait of
+// stage s retires all of stage s + 1 before any wave reads it in phase 4 (s + 1), and every slot
+// half is restaged one phase after its last read, whichever tile the new data belongs to. The DMA
+// never drains between tiles; the prologue runs once per workgroup and GP_PENULT / GP_LAST are the
+// workgroup's last two stages overall.
+// The seam: after the trailing barrier of the p3 MFMA cluster of a tile's last k-step, behind a
+// scalar branch, each wave writes that tile out (alpha, bias, cast, 128 stores) and zeroes its
+// accumulators. The seam has no barrier, so every wave still executes 8 barriers per stage and
+// 1 + 8 x (total stages) in all (wm = 0: 1 + 8 S; wm = 1: 1 + 1 for the stagger + 8 S - 1, the
+// trailing barrier of the workgroup's last stage), set up and evened out once per workgroup. While
+// wm = 0 writes, wm = 1 runs its p3 cluster; while wm = 1 writes, wm = 0 runs the next tile's p0.
+// The k order per accumulator and the epilogue arithmetic are the one-tile kernel's: outputs are
+// bit-equal.
+// vmcnt at the seam: stores count in vmcnt too and may retire out of order with loads, so the next
+// p3 wait may also wait for stores. It cannot wait for too little: LDS-DMA loads retire in order
+// among themselves, and after vmcnt(6) at most 6 operations of any kind are outstanding, hence at
+// most the 6 youngest loads -- the stage the wait is for has landed. (The counter has 6 bits: a
+// wave with 63 operations outstanding stalls at issue, so the 128 stores throttle themselves.)
+// Bias: an ordinary load in the seam would make hipcc drain the DMA with vmcnt(0), so each wave
+// stages its own 64 bias values by one 4-byte-per-lane LDS-DMA (a bf16 bias by the 2-byte form,
+// zero-extended) into its 256 bytes of one of two regions behind the slots (the same __shared__
+// array), the region of tile ordinal j being j & 1. It is issued ahead of p0 of the stage BEFORE
+// the tile's first (the first tile's in the prologue), so that stage's p3 wait retires it (it is
+// older than the three half-tiles the wait leaves in flight) at least a whole k-step and eight
+// barriers before the seam reads it; the region's previous reader is the seam of tile j - 2, which
+// the issuing wave -- the only wave that reads or writes these 256 bytes -- has left by then.
+constexpr int GT_BIAS = 8 * 64 * 2;   // bf16 elements of one bias region: 8 waves x 64 dwords
+
+// 64 consecutive bias values -> 64 LDS dwords at lds_base (wave-uniform), lane l value l. The
+// per-lane offset is made inside the statement (v_mbcnt), not carried through the loop in a VGPR
+// the loop has no room for.
+__device__ __forceinline__ void gt_bias_dma(const void* bias, int bias_bf16, int n, void* lds_base) {
+  const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)LDS_PTR(void, lds_base));
+  unsigned keep, voff;
+  if (bias_bf16)
+    asm volatile(
+        "v_mbcnt_lo_u32_b32 %1, -1, 0\n\t"
+        "v_mbcnt_hi_u32_b32 %1, -1, %1\n\t"
+        "v_lshlrev_b32 %1, 1, %1\n\t"
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 2\n\t"
+        "global_load_lds_ushort %1, %2\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep), "=&v"(voff)
+        : "s"((const bf16*)bias + n), "s"(lds)
+        : "memory");
+  else
+    asm volatile(
+        "v_mbcnt_lo_u32_b32 %1, -1, 0\n\t"
+        "v_mbcnt_hi_u32_b32 %1, -1, %1\n\t"
+        "v_lshlrev_b32 %1, 2, %1\n\t"
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 2\n\t"
+        "global_load_lds_dword %1, %2\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep), "=&v"(voff)
+        : "s"((const bf16*)bias + 2 * n), "s"(lds)
+        : "memory");
+}
+
+// a stage of a workgroup's flattened sequence: tile origin, k offset, ordinal of the tile
+// and its operands at (m0, k) / (n0, k): a piece's source is pa / pb + a per-wave constant
+struct GtCur {
+  int m0, n0, k, j;
+  const bf16* pa;
+  const bf16* pb;
+};
+
+template <bool A_KCONTIG, bool B_KCONTIG>
+__device__ __forceinline__ void gt_origin(GtCur& c, const bf16* A, long long lda, const bf16* B, long long ldb,
+                                          int tiles, int ntn) {
+  // past the workgroup's last tile the origin is never used (GP_PENULT / GP_LAST issue no such load)
+  const int t = xcd_tile((int)blockIdx.x + c.j * (int)gridDim.x, tiles);
+  c.m0 = (t / ntn) * GW_M;
+  c.n0 = (t % ntn) * GW_N;
+  c.pa = A + (A_KCONTIG ? (size_t)c.m0 * lda : (size_t)c.m0);
+  c.pb = B + (B_KCONTIG ? (size_t)c.n0 * ldb : (size_t)c.n0);
+}
+
+template <bool A_KCONTIG, bool B_KCONTIG>
+__device__ __forceinline__ GtCur gt_next(GtCur c, const bf16* A, long long lda, const bf16* B, long long ldb, int Kd,
+                                         int tiles, int ntn) {
+  c.k += BK;
+  if (c.k == Kd) {
+    c.k = 0;
+    ++c.j;
+    gt_origin<A_KCONTIG, B_KCONTIG>(c, A, lda, B, ldb, tiles, ntn);
+  } else {
+    c.pa += A_KCONTIG ? (long long)BK : BK * lda;
+    c.pb += B_KCONTIG ? (long long)BK : BK * ldb;
+  }
+  return c;
+}
+
+// One output element to row base `row` (scalar registers) + voff (per lane) + OFF bytes. An asm store
+// pins the scalar-base form: written in C++, hipcc folds base + voff into 128 per-lane 64-bit
+// pointers and their row arithmetic into the seam (measured: ~800 scalar and ~80 vector instructions
+// per seam and wave). hipcc does not count an asm store; nothing in the kernel waits for one.
+template <int OFF>
+__device__ __forceinline__ void gt_store1(const char* row, unsigned voff, float x) {
+  asm volatile("global_store_dword %0, %1, %2 offset:%3" ::"v"(voff), "v"(x), "s"(row), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void gt_store1(const char* row, unsigned voff, bf16 x) {
+  asm volatile("global_store_short %0, %1, %2 offset:%3" ::"v"(voff), "v"(x), "s"(row), "n"(OFF) : "memory");
+}
+
+// The one-tile kernel's epilogue arithmetic on tile (m0, n0), the bias from this wave's 64 staged
+// dwords, then the accumulators zeroed. Rows are walked with one scalar pointer: a lane's rows are
+// 32 a + 8 q + i (+ 4 h in voff), so the next row is always 1 or 5 rows on; the two 32-column
+// blocks of a row are the store's immediate offset.
+template <typename OutT>
+__device__ __forceinline__ void gt_store(f32x16 (&acc)[4][2], OutT* __restrict__ C, long long ldc, int m0, int n0,
+                                         float alpha, const unsigned* bl, bool has_bias, int bias_bf16, int wm, int wn,
+                                         int lane) {
+  const int h = lane >> 5;
+  float bn[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const unsigned raw = bl[b * 32 + (lane & 31)];
+    bn[b] = has_bias ? __uint_as_float(bias_bf16 ? raw << 16 : raw) : 0.f;
+  }
+  const unsigned voff = (unsigned)((4 * h * ldc + (lane & 31)) * (long long)sizeof(OutT));
+  const long long rs = ldc * (long long)sizeof(OutT);
+  const char* row = (const char*)(C + (size_t)(m0 + wm * 128) * ldc + n0 + wn * 64);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      gt_store1<0>(row, voff, (OutT)(alpha * acc[a][0][v] + bn[0]));
+      gt_store1<32 * (int)sizeof(OutT)>(row, voff, (OutT)(alpha * acc[a][1][v] + bn[1]));
+      row += (v & 3) == 3 ? 5 * rs : rs;
+      asm volatile("" : "+s"(row));   // keep the walk a chain of scalar adds
+    }
+    acc[a][0] = (f32x16){};
+    acc[a][1] = (f32x16){};
+  }
+}
+
+template <bool A_KCONTIG, bool B_KCONTIG, typename OutT>
+__global__ __launch_bounds__(512, 1) void gemm_w8_tiles_kernel(const bf16* __restrict__ A, long long lda,
+                                                               const bf16* __restrict__ B, long long ldb, int N,
+                                                               int Kd, const float* __restrict__ alpha_p,
+                                                               OutT* __restrict__ C, long long ldc,
+                                                               const void* __restrict__ bias, int bias_bf16,
+                                                               int tiles) {
+  __shared__ __attribute__((aligned(16))) bf16 lds[2 * GW_ST + 2 * GT_BIAS];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int ntn = N / GW_N;
+  const int W = gridDim.x;
+  const int cnt = (tiles - (int)blockIdx.x + W - 1) / W;   // this workgroup's tiles, >= 1 (W <= tiles)
+  const int S = cnt * (Kd / BK);                            // its stages
+  const float alpha = alpha_p ? *alpha_p : 1.f;
+  const bool has_bias = bias != nullptr;
+  bf16* const bias_lds = lds + 2 * GW_ST + wave * 128;      // + (j & 1) * GT_BIAS
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = (f32x16){};
+
+  const unsigned va[2] = {gp_voff<A_KCONTIG>(lda, lane, 0), gp_voff<A_KCONTIG>(lda, lane, 1)};
+  const unsigned vb[2] = {gp_voff<B_KCONTIG>(ldb, lane, 0), gp_voff<B_KCONTIG>(ldb, lane, 1)};
+#define GT_NEXT(c) gt_next<A_KCONTIG, B_KCONTIG>(c, A, lda, B, ldb, Kd, tiles, ntn)
+  GtCur c0 = {0, 0, 0, 0, nullptr, nullptr};
+  gt_origin<A_KCONTIG, B_KCONTIG>(c0, A, lda, B, ldb, tiles, ntn);
+  GtCur c1 = GT_NEXT(c0), c2 = GT_NEXT(c1);   // stages s + 1, s + 2
+  const GtLds dma = {(unsigned)(size_t)LDS_PTR(void, lds)};
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+    gp_half<B_KCONTIG, B_KCONTIG>(c0.pb, ldb, 0, 0, dma + GW_A, wave, vb, hh);
+    gp_half<A_KCONTIG, false>(c0.pa, lda, 0, 0, dma, wave, va, hh);
+  }
+  if (has_bias) gt_bias_dma(bias, bias_bf16, c0.n0 + wn * 64, bias_lds);
+  if (S > 1) {
+    gp_half<B_KCONTIG, B_KCONTIG>(c1.pb, ldb, 0, 0, dma + (GW_ST + GW_A), wave, vb, 0);
+    gp_half<B_KCONTIG, B_KCONTIG>(c1.pb, ldb, 0, 0, dma + (GW_ST + GW_A), wave, vb, 1);
+    gp_half<A_KCONTIG, false>(c1.pa, lda, 0, 0, dma + GW_ST, wave, va, 0);
+    TRIAD_VMCNT(GP_LOADS * GP_FLIGHT);
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  if (wm) __builtin_amdgcn_s_barrier();   // the stagger
+  __builtin_amdgcn_sched_barrier(0);
+  // One stage: the next tile's bias if stage s + 1 opens a tile (never in GP_LAST: no stage s + 1),
+  // the k-step, the seam if it closed a tile. The three cursors move on by one stage in p3, which
+  // has no fragment reads to issue (the step took its sources by value); `e` = the stage the
+  // k-step was for.
+  GtCur e = c0;
+  bool bias_next = has_bias && c1.k == 0;
+#define GT_STEP(slot, MODE)                                                                                       \
+  do {                                                                                                            \
+    if (MODE != GP_LAST && bias_next)                                                                             \
+      gt_bias_dma(bias, bias_bf16, c1.n0 + wn * 64, bias_lds + (c1.j & 1) * GT_BIAS);                             \
+    GtLds dst = dma;                                                                                              \
+    asm volatile("" : "+s"(dst.addr));                                                                            \
+    gp_step<A_KCONTIG, B_KCONTIG, MODE>(c1.pa, c2.pa, lda, c2.pb, ldb, 0, 0, 0, 0, 0, lds, dst, slot, wave, lane,  \
+                                        wm, wn, va, vb, acc, [&] {                                                \
+                                          e = c0;                                                                 \
+                                          c0 = c1;                                                                \
+                                          c1 = c2;                                                                \
+                                          c2 = GT_NEXT(c2);                                                       \
+                                          bias_next = has_bias && c1.k == 0;                                      \
+                                        });                                                                       \
+    if (MODE == GP_LAST || e.k + BK == Kd) {                                                                      \
+      gt_store<OutT>(acc, C, ldc, e.m0, e.n0, alpha, (const unsigned*)(bias_lds + (e.j & 1) * GT_BIAS), has_bias,  \
+                     bias_bf16, wm, wn, lane);                                                                    \
+      __builtin_amdgcn_sched_barrier(0);                                                                          \
+    }                                                                                                             \
+  } while (0)
+  int s = 0;
+  for (; s + 3 < S; s += 2) {
+    GT_STEP(0, GP_STEADY);
+    GT_STEP(1, GP_STEADY);
+  }
+  // 1 (S = 1 only), 2 or 3 stages are left and s is even
+  if (S - s == 3) {
+    GT_STEP(0, GP_STEADY);
+    ++s;
+  }
+  if (S - s == 2) {
+    GT_STEP(s & 1, GP_PENULT);
+    ++s;
+  }
+  GT_STEP(s & 1, GP_LAST);
+#undef GT_STEP
+#undef GT_NEXT
+}
+
 // (Measured and not kept, round 4: the eight-wave tile on v_mfma_f32_16x16x32_bf16 -- bit-identical,
 // but 2-30 % slower on every c3 projection-head / backbone shape, profiles/r04_gemm_m16_ab.log; the
 // 16 x 16 x 32 shape pays off in the similarity head's direct-B tile GEMMs, not here.)
@@ -622,10 +903,40 @@ constexpr int kXcdSplit = 8;
 constexpr int kMaxGridY = 65535;
 
 
+// Grid of the multi-tile kernel for `tiles` output tiles on `cus` CUs, 0 = one tile per workgroup.
+// With R = ceil(tiles / cus) dispatch rounds, ceil(tiles / R) workgroups of at most R tiles each:
+// the same makespan in tile-times as the dispatcher's rounds (597 tiles on 256 CUs: 199 workgroups
+// of 3), and the tiles live at one time stay neighbours. The tail of a fractional round is left as
+// it is.
+int w8_workgroups(int tiles, int cus) {
+  const int R = (tiles + cus - 1) / cus;
+  return R <= 1 ? 0 : (tiles + R - 1) / R;
+}
+
+// the multi-tile kernel's per-lane store offset (4 rows of C, in bytes) is a 32-bit register
+constexpr long long kTilesMaxLdc = 1LL << 27;
+
+// CU count of the current device, read once per device ordinal
+int device_cus() {
+  constexpr int kDevs = 64;
+  static std::atomic<int> cache[kDevs];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  int cus = dev >= 0 && dev < kDevs ? cache[dev].load(std::memory_order_relaxed) : 0;
+  if (cus <= 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (dev >= 0 && dev < kDevs) cache[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
+
+// tile_wgs: 0 = the product path (a splits == 1 call in the eight-wave form is routed to the
+// multi-tile kernel when some workgroup would get a second tile); > 0 = the multi-tile kernel on
+// that grid (triad_gemm_bf16_tiles).
 template <bool AK, bool BK_, typename OutT>
 int launch(const void* A, long long lda, const void* B, long long ldb, int M, int N, int Kd, const float* alpha,
            void* C, long long ldc, hipStream_t st, int splits = 1, long long slab_stride = 0,
-           const void* bias = nullptr, int form = 0, int bias_bf16 = 0) {
+           const void* bias = nullptr, int form = 0, int bias_bf16 = 0, int tile_wgs = 0) {
   const int xsplit = (form & kXcdSplit) ? 1 : 0;
   form &= ~kXcdSplit;
   if (M <= 0 || N <= 0 || Kd <= 0) return TRIAD_EINVAL;
@@ -644,9 +955,21 @@ int launch(const void* A, long long lda, const void* B, long long ldb, int M, in
   // 2.94 -> 2.67 ms at M = 1.6 M, N = 512, K = 1536); the split-K weight gradients and the
   // shorter forward shapes keep the smaller tiles
   const bool w4_auto = AK && BK_ && splits == 1 && M >= 65536 && Kd >= 1024;
+  if (tile_wgs) {
+    if (!w4_ok || splits != 1 || tile_wgs < 1 || tile_wgs > (long long)(M / GW_M) * (N / GW_N)) return TRIAD_EINVAL;
+    if (ldc > kTilesMaxLdc) return TRIAD_EINVAL;
+    form = kBigForm;
+  }
   if (form == 0 && w4_ok && w4_auto) form = kBigForm;
   if (w4_ok && (form == 4 || form == 3)) {   // (form 3, the four-wave 256 x 256 tile, was retired in round 5)
     const int nwg = (M / GW_M) * (N / GW_N);
+    if (!tile_wgs && splits == 1 && ldc <= kTilesMaxLdc) tile_wgs = w8_workgroups(nwg, device_cus());
+    if (tile_wgs) {
+      hipLaunchKernelGGL((gemm_w8_tiles_kernel<AK, BK_, OutT>), dim3(tile_wgs), dim3(512), 0, st, (const bf16*)A, lda,
+                         (const bf16*)B, ldb, N, Kd, alpha, (OutT*)C, ldc, bias, bias_bf16, nwg);
+      TRIAD_CHECK_LAUNCH();
+      return TRIAD_OK;
+    }
     hipLaunchKernelGGL((gemm_w8_kernel<AK, BK_, OutT>), dim3(nwg, splits), dim3(512), 0, st, (const bf16*)A, lda,
                        (const bf16*)B, ldb, M, N, Kd, alpha, (OutT*)C, ldc, kps, slab_stride, bias, bias_bf16, xsplit);
     TRIAD_CHECK_LAUNCH();
@@ -688,6 +1011,35 @@ int triad_gemm_bf16_form(const void* A, long long lda, int a_kcontig, const void
   TRIAD_GEMM_CASE(false, true)
   TRIAD_GEMM_CASE(false, false)
 #undef TRIAD_GEMM_CASE
+  return TRIAD_EINVAL;
+}
+
+// Grid the 256 x 256 eight-wave form runs `tiles` output tiles on, on a device of `cus` CUs: the
+// workgroup count of the multi-tile kernel, or 0 when every workgroup gets one tile (the one-tile
+// kernel). Host only.
+int triad_gemm_w8_workgroups(int tiles, int cus) {
+  if (tiles <= 0 || cus <= 0) return TRIAD_EINVAL;
+  return w8_workgroups(tiles, cus);
+}
+
+// The multi-tile eight-wave kernel on a caller-chosen grid, 1 <= workgroups <= (M / 256)(N / 256):
+// workgroup g runs tiles g, g + workgroups, ... back to back. M, N multiples of 256. For tests and
+// tools; the product entry points route themselves (launch()).
+int triad_gemm_bf16_tiles(const void* A, long long lda, int a_kcontig, const void* B, long long ldb, int b_kcontig,
+                          int M, int N, int Kd, const float* alpha, void* C, long long ldc, int out_bf16,
+                          const void* bias, int bias_bf16, int workgroups, hipStream_t stream) {
+  if (workgroups < 1) return TRIAD_EINVAL;
+#define TRIAD_GEMM_T(AK, BKC)                                                                                 \
+  if (!!a_kcontig == AK && !!b_kcontig == BKC)                                                                \
+    return out_bf16 ? launch<AK, BKC, bf16>(A, lda, B, ldb, M, N, Kd, alpha, C, ldc, stream, 1, 0, bias, 0,    \
+                                            !!bias_bf16, workgroups)                                          \
+                    : launch<AK, BKC, float>(A, lda, B, ldb, M, N, Kd, alpha, C, ldc, stream, 1, 0, bias, 0,   \
+                                             !!bias_bf16, workgroups);
+  TRIAD_GEMM_T(true, true)
+  TRIAD_GEMM_T(true, false)
+  TRIAD_GEMM_T(false, true)
+  TRIAD_GEMM_T(false, false)
+#undef TRIAD_GEMM_T
   return TRIAD_EINVAL;
 }
 
