@@ -491,6 +491,31 @@ int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            const unsigned* wk, float p, void* dq, long long dq_sB, long long dq_sN, void* dk,
                            long long dk_sB, long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta,
                            hipStream_t stream);
+/* Key-padding mask (padded caption batches of DistilBERT): the _dropout forms with a per-SAMPLE key mask km
+ * after p, B x ceil(N/32) words, one row per sample shared by its heads; bit j of word kt set = key 32 kt + j
+ * takes part. Bits of keys >= N are ignored; km needs 4-byte alignment (else TRIAD_EINVAL, with every rule of
+ * the _dropout forms); km NULL = no mask (the five entry points above pass NULL). The softmax runs over the
+ * set keys only: a cleared key has probability exactly 0 in out, lse, dq, dk and dv (by selection, whatever
+ * its score and dP), and its dk / dv rows are written as +0. All N positions remain queries. The dropout
+ * keep bit of (bh, q, key) stays element (bh N + q) N + key, so triad_attn_dropmask's words serve masked
+ * calls unchanged. A sample with no key set gives out = +0, lse = -inf, dq = dk = dv = 0. K and V rows of
+ * cleared keys must be FINITE: they still pass through the MFMAs with weight 0, and 0 * NaN is NaN there
+ * as it is in PyTorch.
+ * triad_attn_keymask_pack writes those words from a row-major (B, N) byte mask on the device (bool / u8,
+ * non-zero = keep; bits past N in the last word are written as 0): B * ceil(N/32) words. TRIAD_EINVAL for a
+ * null mask or words, words off 4 bytes, B <= 0 or > 65535, N < 1 or > 320. */
+int triad_attn_keymask_pack(const void* mask, int B, int N, unsigned* words, hipStream_t stream);
+int triad_attn_fwd_keymask(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
+                           long long k_sN, const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D,
+                           float scale, const unsigned* wq, float p, const unsigned* km, void* out, long long out_sB,
+                           long long out_sN, float* lse, hipStream_t stream);
+int triad_attn_bwd_keymask(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
+                           long long k_sN, const void* v, long long v_sB, long long v_sN, const void* o,
+                           long long o_sB, long long o_sN, const void* dout, long long do_sB, long long do_sN,
+                           const float* lse, int B, int H, int N, int D, float scale, const unsigned* wq,
+                           const unsigned* wk, float p, const unsigned* km, void* dq, long long dq_sB,
+                           long long dq_sN, void* dk, long long dk_sB, long long dk_sN, void* dv, long long dv_sB,
+                           long long dv_sN, float* delta, hipStream_t stream);
 
 /* The same attention for longer sequences, 321 <= N <= 2048 (DINOv2-L/14 at 518 px: 1374 tokens;
  * HuBERT-large on 10 s of audio: 499): K / V (forward, dq) or Q / dO (dk, dv) are streamed through LDS

@@ -108,6 +108,11 @@ SIGNATURES = {
     "triad_attn_fwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, i64, i64, vp, vp],
     "triad_attn_bwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32,
                        i32, f32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp],
+    "triad_attn_keymask_pack": [vp, i32, i32, vp, vp],
+    "triad_attn_fwd_keymask": [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, f32, vp, vp,
+                               i64, i64, vp, vp],
+    "triad_attn_bwd_keymask": [vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32,
+                               i32, i32, f32, vp, vp, f32, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp],
     "triad_attn_long_dropmask": [i32, i32, i32, f32, u32, vp, vp, vp],
     "triad_attn_long_fwd": [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, f32, vp, i64, i64,
                             vp, vp],
@@ -141,7 +146,7 @@ BACKBONE_ENTRY_POINTS = frozenset({
     "triad_dropaddln_fwd", "triad_dropaddln_bwd", "triad_gelu_table", "triad_geludrop_fwd", "triad_geludrop_bwd",
     "triad_dropout_keep", "triad_addln_fwd", "triad_addln_bwd", "triad_lora_tn", "triad_attn_dropmask",
     "triad_attn_fwd_dropout", "triad_attn_bwd_dropout", "triad_attn_fwd", "triad_attn_bwd",
-    "triad_attn_long_dropmask", "triad_attn_long_fwd", "triad_attn_long_bwd"})
+    "triad_attn_keymask_pack", "triad_attn_fwd_keymask", "triad_attn_bwd_keymask", "triad_attn_long_dropmask", "triad_attn_long_fwd", "triad_attn_long_bwd"})
 
 
 def hot_path_entry_points():

@@ -20,6 +20,13 @@
 // LDS rows of 64 bf16 (128 B) are stored with the 16-byte chunk swizzle chunk ^ g((row >> 1) & 7),
 // g(k) = (k >> 1) | ((k & 1) << 2): conflict-free for 32-row ds_read_b128 at one chunk and for the
 // 4-row transposed reads.
+// Key-padding mask (MASK instances; AttnArgs::km, one row of ceil(N / 32) words per SAMPLE, bit j of word kt
+// = key 32 kt + j takes part): a cleared key is handled like a key >= N. In the forward and dq kernels the key
+// is the accumulator row, so its bit is tile_bit(w, v, h) of the wave-uniform word km[b * wpr + kt]; in the dkv
+// kernel the key is on the lane, bit kl of this wave's word. Probabilities of cleared keys are SELECTED to 0
+// (never multiplied by 0: with no key set in a sample lse = -inf and exp2(.. - lse2) = +inf), their dk / dv
+// rows are stored as +0, and a sample with no key set gives out = +0, lse = -inf. All N positions stay
+// queries. K / V rows of cleared keys must be finite: they enter the MFMAs with weight 0, and 0 * NaN is NaN.
 // Tensors are (B, N, H, 64) in memory with the head dimension contiguous: element (b, n, h, c)
 // at b * sB + n * sN + h * 64 + c (fused qkv projections and HF's transposed views alike).
 // This file holds the kernels and their launches only: the argument struct AttnArgs, the entry points'
@@ -53,7 +60,7 @@ __device__ __forceinline__ void load_rows2(char* l0, const bf16* b0, long long s
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int NKT, bool DROP>
+template <int NKT, bool DROP, bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2 * NKT * 32 * 128];
   char* kl = lds;
@@ -88,6 +95,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     for (int v = 0; v < 16; ++v)
       if (acc_row(v, h) >= nlast) acc[NKT - 1][v] = -INFINITY;
   }
+  if (MASK) {  // cleared keys leave the softmax like the keys >= N (one wave-uniform word per tile)
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      const unsigned w = a.km[b * a.wpr + kt];
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[kt][v] = tile_bit(w, v, h) ? acc[kt][v] : -INFINITY;
+    }
+  }
   float m = -INFINITY;
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
@@ -95,7 +110,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     for (int v = 0; v < 16; ++v) m = fmaxf(m, acc[kt][v]);
   m = fmaxf(m, __shfl_xor(m, 32));
   const float c2 = a.scale * LOG2E;
-  const float mo = m * c2;
+  // a sample with no key set: m = -inf; -mo = +inf would make every argument NaN (0 keeps them -inf: p = 0)
+  const float mo = MASK && m == -INFINITY ? 0.f : m * c2;
   float l = 0.f;
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
@@ -126,7 +142,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
       o1 = mfma32(frag_tr(vl, c, 32, lane), pf, o1);
     }
   if (!qok) return;
-  const float inv = (DROP ? a.drop_scale : 1.f) / l;
+  if (MASK && l == 0.f) {  // no key set: out = +0 (not 0 / 0), lse = -inf + log 0 = -inf
+    o0 = (f32x16){};
+    o1 = (f32x16){};
+  }
+  const float inv = MASK && l == 0.f ? 0.f : (DROP ? a.drop_scale : 1.f) / l;
   bf16* op = a.out + b * a.out_sB + (long long)q * a.out_sN + hh * HD;
   store_cols(op, o0, inv, h);
   store_cols(op + 32, o1, inv, h);
@@ -134,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 }
 
 // dQ: wave = query tile, query on the lane (the forward's orientation)
-template <int NKT, bool DROP>
+template <int NKT, bool DROP, bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2 * NKT * 32 * 128];
   char* kl = lds;
@@ -180,9 +200,11 @@ __global__ __launch_bounds__(256, 2) void attn_dq_kernel(AttnArgs a) {
     }
     const int nv = a.N - kt * 32;
     const unsigned w = DROP && qok ? a.wq[((long long)bh * a.N + q) * NKT + kt] : 0u;
+    const unsigned wm = MASK ? a.km[b * a.wpr + kt] : ~0u;
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const bool ok = qok && acc_row(v, h) < nv;
+      // (a cleared key, or any key of a sample with none set, where lse = -inf makes e = +inf: selected away)
+      const bool ok = qok && acc_row(v, h) < nv && (!MASK || tile_bit(wm, v, h));
       const float e = __builtin_amdgcn_exp2f(fmaf(s[v], c2, -lse2));
       const float p = ok ? e : 0.f;
       const float dpv = DROP ? (tile_bit(w, v, h) ? dp[v] * a.drop_scale : 0.f) : dp[v];
@@ -203,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void attn_dq_kernel(AttnArgs a) {
 }
 
 // dK, dV: wave = key tile, key on the lane
-template <int NQT, bool DROP>
+template <int NQT, bool DROP, bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[2 * NQT * 32 * 128];
   __shared__ float stat[2][NQT * 32];
@@ -213,7 +235,10 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, kl = lane & 31;
   const int kt = blockIdx.x * 4 + wave;
   const int key = kt * 32 + kl;
-  const bool kok = key < a.N;
+  // a cleared key is treated like a key >= N (p = 0 by selection: with no key set lse = -inf and e = +inf),
+  // except that its dk / dv rows are written (as +0)
+  const unsigned wm = MASK && kt * 32 < a.N ? a.km[b * a.wpr + kt] : ~0u;   // this wave's tile of the sample's word row
+  const bool kok = key < a.N && ((wm >> kl) & 1u);
   bf16x8 kf[4], vf[4];  // requested before the block's Q / dO staging (latency overlapped)
   {
     const long long kk = kok ? key : 0;
@@ -283,57 +308,122 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnArgs a) {
   for (int v = 0; v < 16; ++v) {
     const int kr = kt * 32 + acc_row(v, h);
     if (kr < a.N) {
+      const bool set = !MASK || tile_bit(wm, v, h);   // rows of cleared keys: +0 by selection
       bf16* dkp = a.dk + b * a.dk_sB + (long long)kr * a.dk_sN + hh * HD + kl;
       bf16* dvp = a.dv + b * a.dv_sB + (long long)kr * a.dv_sN + hh * HD + kl;
-      dkp[0] = (bf16)(dk0[v] * a.scale);
-      dkp[32] = (bf16)(dk1[v] * a.scale);
-      dvp[0] = (bf16)dv0[v];
-      dvp[32] = (bf16)dv1[v];
+      dkp[0] = (bf16)(set ? dk0[v] * a.scale : 0.f);
+      dkp[32] = (bf16)(set ? dk1[v] * a.scale : 0.f);
+      dvp[0] = (bf16)(set ? dv0[v] : 0.f);
+      dvp[32] = (bf16)(set ? dv1[v] : 0.f);
     }
   }
 }
 
-#define ATTN_SWITCH(KERNEL, DR, NT, GRID, ARGS)                                                 \
-  switch (NT) {                                                                                \
-    case 1: hipLaunchKernelGGL((KERNEL<1, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 2: hipLaunchKernelGGL((KERNEL<2, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 3: hipLaunchKernelGGL((KERNEL<3, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 4: hipLaunchKernelGGL((KERNEL<4, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 5: hipLaunchKernelGGL((KERNEL<5, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 6: hipLaunchKernelGGL((KERNEL<6, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 7: hipLaunchKernelGGL((KERNEL<7, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 8: hipLaunchKernelGGL((KERNEL<8, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    case 9: hipLaunchKernelGGL((KERNEL<9, DR>), GRID, dim3(256), 0, stream, ARGS); break;       \
-    default: hipLaunchKernelGGL((KERNEL<10, DR>), GRID, dim3(256), 0, stream, ARGS); break;     \
+// (B, N) bytes (non-zero = keep) -> B x ceil(N / 32) key-mask words: one thread per word, bits of keys >= N zero
+__global__ __launch_bounds__(256) void attn_keymask_pack_kernel(const unsigned char* __restrict__ mask, int B, int N,
+                                                                int wpr, unsigned* __restrict__ words) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * wpr) return;
+  const int b = i / wpr, kt = i - b * wpr;
+  const int n = min(32, N - kt * 32);
+  const unsigned char* row = mask + (long long)b * N + kt * 32;
+  unsigned w = 0u;
+  for (int j = 0; j < n; ++j) w |= (row[j] != 0 ? 1u : 0u) << j;
+  words[i] = w;
+}
+
+#define ATTN_SWITCH_NT(KERNEL, DR, MK, NT, GRID, ARGS)                                              \
+  switch (NT) {                                                                                    \
+    case 1: hipLaunchKernelGGL((KERNEL<1, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 2: hipLaunchKernelGGL((KERNEL<2, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 3: hipLaunchKernelGGL((KERNEL<3, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 4: hipLaunchKernelGGL((KERNEL<4, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 5: hipLaunchKernelGGL((KERNEL<5, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 6: hipLaunchKernelGGL((KERNEL<6, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 7: hipLaunchKernelGGL((KERNEL<7, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 8: hipLaunchKernelGGL((KERNEL<8, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    case 9: hipLaunchKernelGGL((KERNEL<9, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;       \
+    default: hipLaunchKernelGGL((KERNEL<10, DR, MK>), GRID, dim3(256), 0, stream, ARGS); break;     \
+  }
+// the instance by (dropout words given, key mask given)
+#define ATTN_SWITCH(KERNEL, DROP, MASK, NT, GRID, ARGS)                          \
+  if (DROP) {                                                                   \
+    if (MASK) { ATTN_SWITCH_NT(KERNEL, true, true, NT, GRID, ARGS) }            \
+    else { ATTN_SWITCH_NT(KERNEL, true, false, NT, GRID, ARGS) }                \
+  } else {                                                                      \
+    if (MASK) { ATTN_SWITCH_NT(KERNEL, false, true, NT, GRID, ARGS) }           \
+    else { ATTN_SWITCH_NT(KERNEL, false, false, NT, GRID, ARGS) }               \
   }
 
 static_assert(MAX_N_SHORT == 10 * 32, "ATTN_SWITCH instantiates 1 .. 10 tiles of 32");
 }  // namespace
 
-// (the keep words wq / wk come from triad_attn_dropmask, attention_mask.hip)
+// (the keep words wq / wk come from triad_attn_dropmask, attention_mask.hip; the key-mask words km from
+// triad_attn_keymask_pack below)
 extern "C" {
+
+int triad_attn_keymask_pack(const void* mask, int B, int N, unsigned* words, hipStream_t stream) {
+  if (!mask || !words || ((uintptr_t)words & 3) || B <= 0 || N < 1 || N > MAX_N_SHORT || B > 65535)
+    return TRIAD_EINVAL;
+  const int wpr = (N + 31) / 32;
+  hipLaunchKernelGGL(attn_keymask_pack_kernel, dim3((B * wpr + 255) / 256), dim3(256), 0, stream,
+                     (const unsigned char*)mask, B, N, wpr, words);
+  TRIAD_CHECK_LAUNCH();
+  return TRIAD_OK;
+}
+
+int triad_attn_fwd_keymask(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
+                           long long k_sN, const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D,
+                           float scale, const unsigned* wq, float p, const unsigned* km, void* out, long long out_sB,
+                           long long out_sN, float* lse, hipStream_t stream) {
+  AttnArgs a = {};
+  if (!attn_fwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, B, H, N, D, scale, wq, p,
+                     {out, out_sB, out_sN}, lse) ||
+      ((uintptr_t)km & 3))
+    return TRIAD_EINVAL;
+  a.km = km;
+  const int nt = (N + 31) / 32;
+  const dim3 grid = attn_grid(B, H, N);
+  ATTN_SWITCH(attn_fwd_kernel, wq, km, nt, grid, a)
+  TRIAD_CHECK_LAUNCH();
+  return TRIAD_OK;
+}
 
 int triad_attn_fwd_dropout(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
                            long long k_sN, const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D,
                            float scale, const unsigned* wq, float p, void* out, long long out_sB, long long out_sN,
                            float* lse, hipStream_t stream) {
-  AttnArgs a = {};
-  if (!attn_fwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, B, H, N, D, scale, wq, p,
-                     {out, out_sB, out_sN}, lse))
-    return TRIAD_EINVAL;
-  const int nt = (N + 31) / 32;
-  const dim3 grid = attn_grid(B, H, N);
-  if (wq) { ATTN_SWITCH(attn_fwd_kernel, true, nt, grid, a) }
-  else { ATTN_SWITCH(attn_fwd_kernel, false, nt, grid, a) }
-  TRIAD_CHECK_LAUNCH();
-  return TRIAD_OK;
+  return triad_attn_fwd_keymask(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, B, H, N, D, scale, wq, p, nullptr, out,
+                                out_sB, out_sN, lse, stream);
 }
 
 int triad_attn_fwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
                    const void* v, long long v_sB, long long v_sN, int B, int H, int N, int D, float scale, void* out,
                    long long out_sB, long long out_sN, float* lse, hipStream_t stream) {
-  return triad_attn_fwd_dropout(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, B, H, N, D, scale, nullptr, 0.f, out,
-                                out_sB, out_sN, lse, stream);
+  return triad_attn_fwd_keymask(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, B, H, N, D, scale, nullptr, 0.f, nullptr,
+                                out, out_sB, out_sN, lse, stream);
+}
+
+int triad_attn_bwd_keymask(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
+                           long long k_sN, const void* v, long long v_sB, long long v_sN, const void* o,
+                           long long o_sB, long long o_sN, const void* dout, long long do_sB, long long do_sN,
+                           const float* lse, int B, int H, int N, int D, float scale, const unsigned* wq,
+                           const unsigned* wk, float p, const unsigned* km, void* dq, long long dq_sB,
+                           long long dq_sN, void* dk, long long dk_sB, long long dk_sN, void* dv, long long dv_sB,
+                           long long dv_sN, float* delta, hipStream_t stream) {
+  AttnArgs a = {};
+  if (!attn_bwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, {o, o_sB, o_sN},
+                     {dout, do_sB, do_sN}, lse, B, H, N, D, scale, wq, wk, p, {dq, dq_sB, dq_sN}, {dk, dk_sB, dk_sN},
+                     {dv, dv_sB, dv_sN}, delta) ||
+      ((uintptr_t)km & 3))
+    return TRIAD_EINVAL;
+  a.km = km;
+  const int nt = (N + 31) / 32;
+  const dim3 grid = attn_grid(B, H, N);
+  ATTN_SWITCH(attn_dq_kernel, wq, km, nt, grid, a)
+  ATTN_SWITCH(attn_dkv_kernel, wq, km, nt, grid, a)
+  TRIAD_CHECK_LAUNCH();
+  return TRIAD_OK;
 }
 
 int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB,
@@ -343,22 +433,9 @@ int triad_attn_bwd_dropout(const void* q, long long q_sB, long long q_sN, const 
                            const unsigned* wk, float p, void* dq, long long dq_sB, long long dq_sN, void* dk,
                            long long dk_sB, long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta,
                            hipStream_t stream) {
-  AttnArgs a = {};
-  if (!attn_bwd_args(a, ATTN_SHORT, {q, q_sB, q_sN}, {k, k_sB, k_sN}, {v, v_sB, v_sN}, {o, o_sB, o_sN},
-                     {dout, do_sB, do_sN}, lse, B, H, N, D, scale, wq, wk, p, {dq, dq_sB, dq_sN}, {dk, dk_sB, dk_sN},
-                     {dv, dv_sB, dv_sN}, delta))
-    return TRIAD_EINVAL;
-  const int nt = (N + 31) / 32;
-  const dim3 grid = attn_grid(B, H, N);
-  if (wq) {
-    ATTN_SWITCH(attn_dq_kernel, true, nt, grid, a)
-    ATTN_SWITCH(attn_dkv_kernel, true, nt, grid, a)
-  } else {
-    ATTN_SWITCH(attn_dq_kernel, false, nt, grid, a)
-    ATTN_SWITCH(attn_dkv_kernel, false, nt, grid, a)
-  }
-  TRIAD_CHECK_LAUNCH();
-  return TRIAD_OK;
+  return triad_attn_bwd_keymask(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, o, o_sB, o_sN, dout, do_sB, do_sN, lse,
+                                B, H, N, D, scale, wq, wk, p, nullptr, dq, dq_sB, dq_sN, dk, dk_sB, dk_sN, dv, dv_sB,
+                                dv_sN, delta, stream);
 }
 
 int triad_attn_bwd(const void* q, long long q_sB, long long q_sN, const void* k, long long k_sB, long long k_sN,
@@ -366,9 +443,10 @@ int triad_attn_bwd(const void* q, long long q_sB, long long q_sN, const void* k,
                    const void* dout, long long do_sB, long long do_sN, const float* lse, int B, int H, int N, int D,
                    float scale, void* dq, long long dq_sB, long long dq_sN, void* dk, long long dk_sB,
                    long long dk_sN, void* dv, long long dv_sB, long long dv_sN, float* delta, hipStream_t stream) {
-  return triad_attn_bwd_dropout(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, o, o_sB, o_sN, dout, do_sB, do_sN, lse,
-                                B, H, N, D, scale, nullptr, nullptr, 0.f, dq, dq_sB, dq_sN, dk, dk_sB, dk_sN, dv,
-                                dv_sB, dv_sN, delta, stream);
+  return triad_attn_bwd_keymask(q, q_sB, q_sN, k, k_sB, k_sN, v, v_sB, v_sN, o, o_sB, o_sN, dout, do_sB, do_sN, lse,
+                                B, H, N, D, scale, nullptr, nullptr, 0.f, nullptr, dq, dq_sB, dq_sN, dk, dk_sB, dk_sN,
+                                dv, dv_sB, dv_sN, delta, stream);
 }
 
 }  // extern "C"
+

@@ -84,6 +84,10 @@ struct AttnArgs {
   const unsigned *wq, *wk;
   int wpr;          // words per mask row (attn_wpr)
   float drop_scale;
+  // key-padding mask of the whole-sequence kernels (MASK instances; nullptr = none): km[b * wpr + kt], one
+  // row of ceil(N / 32) words per SAMPLE (all heads share it), bit j = key 32 kt + j takes part; bits of
+  // keys >= N are ignored. Last, so that the fields above keep their kernarg offsets.
+  const unsigned* km;
 };
 
 // The two kernel families as the checks see them: the token range, and whether a lane reads the two

@@ -18,6 +18,7 @@ Offline differences (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import re
@@ -255,8 +256,12 @@ class TextEmbedder(nn.Module):
         no_pad = not mask.is_cuda and bool(mask.all())
         inputs = {k: (_lib.h2d(v, device) if not v.is_cuda and device.type == "cuda" else v.to(device))
                   for k, v in inputs.items()}
-        h = self.encoder(input_ids=inputs["input_ids"],
-                         attention_mask=None if no_pad else inputs["attention_mask"]).last_hidden_state
+        # A padded batch: the fused DistilBERT takes the (B, Nt) mask from this context (the encoder hands
+        # its transformer only the 4-D mask built from it); any other encoder has no such context.
+        key_mask = None if no_pad else inputs["attention_mask"]
+        context = getattr(self.encoder, "triad_key_mask", None)
+        with context(key_mask) if context is not None and key_mask is not None else contextlib.nullcontext():
+            h = self.encoder(input_ids=inputs["input_ids"], attention_mask=key_mask).last_hidden_state
         return _project(self, h), inputs["attention_mask"]
 
 

@@ -19,11 +19,12 @@ tests pin the kernels against torch on the SAME masks (triad_dropout_keep).
 """
 from __future__ import annotations
 
+import contextlib
 import types
 
 import torch
 
-from ._lib import call, ptr, stream_ptr
+from ._lib import TriadError, call, ptr, stream_ptr
 
 
 class _Seeds:
@@ -168,19 +169,23 @@ def _attn_parts(attn):
             float(attn.dropout.p))
 
 
-def self_attention(attn, x):
-    """transformers HubertAttention / DistilBertSelfAttention forward (self-attention, no mask)
-    with q / k / v as ONE projection GEMM (linear.qkv_projection) and the fused-qkv HIP
-    attention kernels on its output; anything the fused form does not cover runs the module."""
+def self_attention(attn, x, key_mask=None):
+    """transformers HubertAttention / DistilBertSelfAttention forward (self-attention) with q / k / v
+    as ONE projection GEMM (linear.qkv_projection) and the fused-qkv HIP attention kernels on its
+    output; anything the fused form does not cover runs the module. key_mask: (B, N) device mask of
+    the keys that take part, or its packed words (attention.pack_key_mask); the module has no way to
+    take it, so a masked call the fused form does not cover raises TriadError (callers gate on it)."""
     from . import attention as A
     from .linear import qkv_eligible, qkv_projection
     B, N, E = x.shape
     q, k, v, o, H, d, scaling, p = _attn_parts(attn)
     if not (qkv_eligible(q, k, v, x) and q.out_features == k.out_features == v.out_features == E == H * d
             and A.supported(x, N, d) and not getattr(attn, "is_causal", False)):
+        if key_mask is not None:
+            raise TriadError(f"self_attention: a key mask needs the fused form ({N} tokens, head dim {d})")
         return attn(x)[0]
     p = p if attn.training else 0.0
-    return o(A.attention_qkv(qkv_projection(q, k, v, x), H, scaling, dropout=p))
+    return o(A.attention_qkv(qkv_projection(q, k, v, x), H, scaling, dropout=p, key_mask=key_mask))
 
 
 def fused_layer(layer, res, res_b, seeds):
@@ -244,19 +249,39 @@ def install_fused_encoder(hubert):
 # TransformerBlock: h1 = sa_LN(attn(h) + h); h2 = out_LN(dropout(lin2(gelu(lin1(h1)))) + h1),
 # the same passes with p = 0 where DistilBERT has no dropout.
 
-def fused_distilbert_block(block, res, res_b, seeds):
+def fused_distilbert_block(block, res, res_b, seeds, key_mask=None):
     ffn = block.ffn
     p = ffn.dropout.p if block.training else 0.0
-    a = self_attention(block.attention, res_b)
+    a = self_attention(block.attention, res_b, key_mask)
     h1, h1b = drop_add_ln(res, a, block.sa_layer_norm, 0.0, 0)
     v = gelu_drop(ffn.lin1(h1b), 0.0, 0)
     return drop_add_ln(h1, ffn.lin2(v), block.output_layer_norm, p, seeds())
 
 
+def _key_mask_for(tr, hidden_states, attention_mask):
+    """The 2-D key mask behind the mask DistilBertModel.forward built for this call, or None: the one
+    the encoder was handed for the duration of the call (install_fused_distilbert's key_mask context),
+    if it is a device tensor of the hidden states' (B, N) that the masked kernels take. The 4-D mask
+    itself is never inspected: it is materialised per query, and that it does not depend on the query
+    could only be checked by reading it back."""
+    from . import attention as A
+    km = getattr(tr, "_triad_key_mask", None)
+    cfg = tr.config
+    if (attention_mask is None or km is None or not km.is_cuda or km.dim() != 2
+            or tuple(km.shape) != tuple(hidden_states.shape[:2]) or km.shape[1] > A.MAX_TOKENS
+            or cfg.dim != cfg.n_heads * A.HEAD_DIM or km.shape[0] * cfg.n_heads > A.MAX_SEQUENCES):
+        return None
+    return km
+
+
 def _distilbert_transformer_forward(self, hidden_states, attention_mask=None, **kwargs):
-    """transformers DistilBERT Transformer.forward with the fused residual / LayerNorm passes."""
+    """transformers DistilBERT Transformer.forward with the fused residual / LayerNorm passes. A padded
+    batch takes them too when the encoder's key_mask context holds the (B, N) mask of this call (packed
+    once for all layers); a mask that arrives without one goes to the stock forward."""
     cfg = self.config
-    if not (hidden_states.is_cuda and attention_mask is None and not kwargs.get("output_attentions")
+    key_mask = _key_mask_for(self, hidden_states, attention_mask)
+    if not (hidden_states.is_cuda and (attention_mask is None or key_mask is not None)
+            and not kwargs.get("output_attentions")
             and not kwargs.get("output_hidden_states") and torch.is_autocast_enabled("cuda")
             and torch.get_autocast_dtype("cuda") == torch.bfloat16 and cfg.dim % 256 == 0 and cfg.dim <= 1024
             and cfg.activation == "gelu" and getattr(cfg, "chunk_size_feed_forward", 0) == 0
@@ -265,17 +290,35 @@ def _distilbert_transformer_forward(self, hidden_states, attention_mask=None, **
     from transformers.modeling_outputs import BaseModelOutput
     res = hidden_states.float()
     res_b = res.to(torch.bfloat16)
+    if key_mask is not None:
+        from . import attention as A
+        key_mask = A.pack_key_mask(key_mask)
     for block in self.layer:
-        res, res_b = fused_distilbert_block(block, res, res_b, self._triad_seeds)
+        res, res_b = fused_distilbert_block(block, res, res_b, self._triad_seeds, key_mask)
     return BaseModelOutput(last_hidden_state=res)
 
 
+@contextlib.contextmanager
+def _key_mask_context(self, key_mask):
+    """`with encoder.triad_key_mask(mask): encoder(input_ids=..., attention_mask=mask)`: hands the (B, N)
+    mask of this call to the encoder's transformer, which otherwise sees only the 4-D mask built from it."""
+    tr = self.transformer
+    prev = getattr(tr, "_triad_key_mask", None)
+    tr._triad_key_mask = key_mask
+    try:
+        yield
+    finally:
+        tr._triad_key_mask = prev
+
+
 def install_fused_distilbert(encoder):
-    """Swap a DistilBertModel's Transformer.forward for the fused one (per instance)."""
+    """Swap a DistilBertModel's Transformer.forward for the fused one (per instance), and give the
+    model `triad_key_mask(mask)`, the context in which a padded batch takes it too."""
     tr = getattr(encoder, "transformer", None)
     if tr is not None and hasattr(tr, "layer") and not hasattr(tr, "_triad_stock_forward"):
         tr._triad_stock_forward = tr.forward
         tr._triad_seeds = _Seeds()
         tr.config = encoder.config
         tr.forward = types.MethodType(_distilbert_transformer_forward, tr)
+        encoder.triad_key_mask = types.MethodType(_key_mask_context, encoder)
     return encoder
