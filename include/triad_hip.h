@@ -600,6 +600,31 @@ int triad_geludrop_bwd(const void* u, const void* dv, long long n, float p, unsi
                        hipStream_t stream);
 int triad_dropout_keep(long long n, float p, unsigned seed, void* out, hipStream_t stream);
 
+/* HuBERT pre-LN ("stable layer norm") residual pass (transformers HubertEncoderLayerStableLayerNorm under bf16
+ * autocast, HuBERT-large; csrc/postln.hip). The residual stream is bf16; LayerNorm's output feeds only the branch.
+ * Keep bits, M, D, p and eps rules as above; res, y, res_out, z, dz, dres, dy are bf16 [M][D], w, b fp32 [D].
+ * triad_preln_fwd: yd = keep ? bf16(float(y) scale) : 0, z = bf16(float(res) + yd), res_out = z;
+ *                  mean / rstd over float(z) (two-pass); n = (float(z) - mean) rstd w + b, n_out = bf16(n), or
+ *                  fp32 n when n_is_f32 (the encoder's final norm). y == NULL: z = res, res_out is not written
+ *                  (and may be NULL), p and seed are not used.
+ * triad_preln_bwd: xh = (float(z) - mean) rstd, g = float(dz) + LN'(dn) at xh in fp32, dres = bf16(g),
+ *                  dy = keep ? bf16(float(dres) scale) : 0. dz: the gradient arriving on res_out, dn: on n_out
+ *                  (bf16, or fp32 when dn_is_f32); either may be NULL, not both (z, mean, rstd are read only with
+ *                  dn). dy == NULL when the forward had no y. part: triad_preln_bwd_blocks(M) x 2 x D fp32
+ *                  dgamma / dbeta partials in triad_dropaddln_bwd's layout (zeros without dn); reduce with
+ *                  triad_sum_slabs. No atomics: repeats are bit-identical.
+ * TRIAD_EINVAL before any launch unless: every pointer but y, res_out (without y), dz, dn and dy non-NULL; bf16
+ * tensors 8-byte aligned (an optional one that is given too: a dy that is given has y's form, a bf16 [M][D]
+ * tensor 8-byte aligned); w, b and an fp32 n_out / dn 16-byte aligned; mean, rstd, part 4-byte aligned; dz or
+ * dn given. */
+int triad_preln_fwd(const void* res, const void* y, const float* w, const float* b, float eps, int M, int D, float p,
+                    unsigned seed, void* res_out, void* n_out, int n_is_f32, float* mean, float* rstd,
+                    hipStream_t stream);
+int triad_preln_bwd_blocks(int M);
+int triad_preln_bwd(const void* dz, const void* dn, int dn_is_f32, const void* z, const float* mean, const float* rstd,
+                    const float* w, int M, int D, float p, unsigned seed, void* dres, void* dy, float* part,
+                    hipStream_t stream);
+
 /* Materialising debug path (csrc/dense.hip; SURVEY §8b keeps the reference's small-B methods):
  * S = token similarities fp32 (Bq, Bk, Nq, Nk) as model.py:384-387 / 502-505 return them.
  * triad_dense_nparts(n): number of per-block partials the reductions below write for n elements.

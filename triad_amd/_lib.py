@@ -96,6 +96,9 @@ SIGNATURES = {
     "triad_geludrop_fwd": [vp, i64, f32, u32, vp, vp, vp],
     "triad_geludrop_bwd": [vp, vp, i64, f32, u32, vp, vp, vp],
     "triad_dropout_keep": [i64, f32, u32, vp, vp],
+    "triad_preln_fwd": [vp, vp, vp, vp, f32, i32, i32, f32, u32, vp, vp, i32, vp, vp, vp],
+    "triad_preln_bwd_blocks": [i32],
+    "triad_preln_bwd": [vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, u32, vp, vp, vp, vp],
     "triad_addln_fwd": [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, i32, vp, vp, vp],
     "triad_addln_bwd": [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
     "triad_lora_tn_blocks": [i32],
@@ -130,6 +133,7 @@ RESTYPES = {"triad_pairsim_nparts": C.c_int, "triad_chgn_workspace_bytes": C.c_l
             "triad_conv0_dw_workspace_bytes": C.c_longlong, "triad_gelu_table_bytes": C.c_longlong,
             "triad_posconv_dw_part_bytes": C.c_longlong,
             "triad_lora_tn_blocks": C.c_int, "triad_dropaddln_bwd_blocks": C.c_int,
+            "triad_preln_bwd_blocks": C.c_int,
             "triad_colsum_splits": C.c_int, "triad_colsum_dma_splits": C.c_int, "triad_dense_nparts": C.c_int,
             "triad_rowpanel_count": C.c_int, "triad_gemm_w8_workgroups": C.c_int}
 
@@ -144,7 +148,7 @@ BACKBONE_ENTRY_POINTS = frozenset({
     "triad_c0gn_fwd",
     "triad_posconv", "triad_posconv_dw", "triad_gemm_bf16_splitk", "triad_rows_nt", "triad_lora_update",
     "triad_dropaddln_fwd", "triad_dropaddln_bwd", "triad_gelu_table", "triad_geludrop_fwd", "triad_geludrop_bwd",
-    "triad_dropout_keep", "triad_addln_fwd", "triad_addln_bwd", "triad_lora_tn", "triad_attn_dropmask",
+    "triad_dropout_keep", "triad_preln_fwd", "triad_preln_bwd", "triad_addln_fwd", "triad_addln_bwd", "triad_lora_tn", "triad_attn_dropmask",
     "triad_attn_fwd_dropout", "triad_attn_bwd_dropout", "triad_attn_fwd", "triad_attn_bwd",
     "triad_attn_keymask_pack", "triad_attn_fwd_keymask", "triad_attn_bwd_keymask", "triad_attn_long_dropmask", "triad_attn_long_fwd", "triad_attn_long_bwd"})
 

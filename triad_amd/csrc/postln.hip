@@ -14,6 +14,8 @@
 // element, keep iff >= round(p * 65536); forward and backward regenerate the same bits
 // (triad_dropout_keep exposes them for tests). The roundings follow the autocast chain
 // (bf16 dropout output, fp32 add / LayerNorm, bf16 GELU output).
+// HuBERT-large (stable layer norm, pre-LN) keeps a bf16 stream; its residual pass is preln_fwd / _bwd
+// further down, on the same keep bits, statistics and partial layout.
 #include "common.h"
 
 namespace {
@@ -149,6 +151,155 @@ __global__ __launch_bounds__(256) void dropaddln_bwd_kernel(const float* __restr
       }
       *(f32x4*)(dres + e) = dz;
       *(bf16x4*)(dy + e) = yb;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      red[wave][0][i * 256 + lane * 4 + c] = gw[i][c];
+      red[wave][1][i * 256 + lane * 4 + c] = gb[i][c];
+    }
+  __syncthreads();
+  for (int t = threadIdx.x; t < 2 * D; t += 256) {
+    const int which = t / D, col = t % D;
+    part[((long long)blockIdx.x * 2 + which) * D + col] =
+        red[0][which][col] + red[1][which][col] + red[2][which][col] + red[3][which][col];
+  }
+}
+
+// ---- pre-LN (stable layer norm: transformers HubertEncoderLayerStableLayerNorm, HuBERT-large) ----
+// Under autocast the residual stream is bf16 and LayerNorm's fp32 output feeds only the branch:
+//   preln_fwd: z = bf16(res + bf16(y * keep / (1 - p))) (the stream, written back as res_out; without
+//              y: z = res), n = LN(z) as bf16 (the next GEMM's operand) or fp32 (the encoder's final
+//              norm), per-row mean / rstd;
+//   preln_bwd: g = dz + LN'(dn) at z in fp32 (dz: the gradient arriving on the stream, dn: on n),
+//              dres = bf16(g), dy = bf16(dres * keep / (1 - p)); per-block dgamma / dbeta partials.
+// Same element -> keep-bit mapping as load_z; the backward reads z, not res and y.
+template <int NB>
+__global__ __launch_bounds__(256) void preln_fwd_kernel(const bf16* __restrict__ res, const bf16* __restrict__ y,
+                                                        const float* __restrict__ w, const float* __restrict__ b,
+                                                        float eps, int M, unsigned seed, unsigned thr, float scale,
+                                                        bf16* __restrict__ res_out, void* __restrict__ n_out,
+                                                        int n_is_f32, float* __restrict__ mean_out,
+                                                        float* __restrict__ rstd_out) {
+  constexpr int D = NB * 256;
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  float v[NB][4];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const long long e = row * D + i * 256 + lane * 4;
+    const bf16x4 r = *(const bf16x4*)(res + e);
+    if (y) {
+      const bf16x4 yv = *(const bf16x4*)(y + e);
+      const unsigned k = keep_pair((unsigned long long)e >> 1, seed, thr) | (keep_pair(((unsigned long long)e >> 1) + 1, seed, thr) << 2);
+      bf16x4 zb;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        zb[c] = (bf16)((float)r[c] + drop((float)yv[c], (k >> c) & 1u, scale));
+        v[i][c] = (float)zb[c];
+      }
+      *(bf16x4*)(res_out + e) = zb;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[i][c] = (float)r[c];
+    }
+  }
+  float mean, rstd;
+  stats<NB>(v, eps, mean, rstd);
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int c0 = i * 256 + lane * 4;
+    const f32x4 wv = *(const f32x4*)(w + c0);
+    const f32x4 bv = *(const f32x4*)(b + c0);
+    f32x4 o;
+    bf16x4 ob;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      o[c] = (v[i][c] - mean) * rstd * wv[c] + bv[c];
+      ob[c] = (bf16)o[c];
+    }
+    if (n_is_f32) *(f32x4*)((float*)n_out + row * D + c0) = o;
+    else *(bf16x4*)((bf16*)n_out + row * D + c0) = ob;
+  }
+  if (lane == 0) {
+    mean_out[row] = mean;
+    rstd_out[row] = rstd;
+  }
+}
+
+// grid-stride over rows and per-block partials as dropaddln_bwd_kernel (the same part layout)
+template <int NB>
+__global__ __launch_bounds__(256) void preln_bwd_kernel(const bf16* __restrict__ dz, const void* __restrict__ dn,
+                                                        int dn_is_f32, const bf16* __restrict__ z,
+                                                        const float* __restrict__ mean_in,
+                                                        const float* __restrict__ rstd_in, const float* __restrict__ w,
+                                                        int M, unsigned seed, unsigned thr, float scale,
+                                                        bf16* __restrict__ dres, bf16* __restrict__ dy,
+                                                        float* __restrict__ part) {
+  constexpr int D = NB * 256;
+  __shared__ float red[4][2][D];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float gw[NB][4] = {}, gb[NB][4] = {};
+  for (long long row = (long long)blockIdx.x * 4 + wave; row < M; row += (long long)gridDim.x * 4) {
+    float xh[NB][4], wd[NB][4];
+    float c1 = 0.f, c2 = 0.f, rstd = 0.f;
+    if (dn) {
+      const float mean = mean_in[row];
+      rstd = rstd_in[row];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const int c0 = i * 256 + lane * 4;
+        const long long e = row * D + c0;
+        const bf16x4 zv = *(const bf16x4*)(z + e);
+        f32x4 d;
+        if (dn_is_f32) d = *(const f32x4*)((const float*)dn + e);
+        else {
+          const bf16x4 t = *(const bf16x4*)((const bf16*)dn + e);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) d[c] = (float)t[c];
+        }
+        const f32x4 wv = *(const f32x4*)(w + c0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          xh[i][c] = ((float)zv[c] - mean) * rstd;
+          gw[i][c] = fmaf(d[c], xh[i][c], gw[i][c]);
+          gb[i][c] += d[c];
+          wd[i][c] = wv[c] * d[c];
+          s1 += wd[i][c];
+          s2 = fmaf(wd[i][c], xh[i][c], s2);
+        }
+      }
+      c1 = wave_sum(s1) / D;
+      c2 = wave_sum(s2) / D;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const long long e = row * D + i * 256 + lane * 4;
+      f32x4 g = {0.f, 0.f, 0.f, 0.f};
+      if (dz) {
+        const bf16x4 t = *(const bf16x4*)(dz + e);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g[c] = (float)t[c];
+      }
+      if (dn) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g[c] += rstd * (wd[i][c] - c1 - xh[i][c] * c2);
+      }
+      bf16x4 rb;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) rb[c] = (bf16)g[c];
+      *(bf16x4*)(dres + e) = rb;
+      if (dy) {
+        const unsigned k = keep_pair((unsigned long long)e >> 1, seed, thr) | (keep_pair(((unsigned long long)e >> 1) + 1, seed, thr) << 2);
+        bf16x4 yb;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) yb[c] = (bf16)drop((float)rb[c], (k >> c) & 1u, scale);
+        *(bf16x4*)(dy + e) = yb;
+      }
     }
   }
 #pragma unroll
@@ -341,6 +492,55 @@ int triad_dropaddln_bwd(const float* dh, const void* dhb, const float* res, cons
   }
   DAL_B(1) DAL_B(2) DAL_B(3) DAL_B(4)
 #undef DAL_B
+  return TRIAD_EINVAL;
+}
+
+// Pre-LN pass of the bf16 stream: res_out = z = bf16(res + dropout(y)), n_out = LN(z) as bf16 or fp32
+// (n_is_f32). y == NULL: z = res, res_out (which may then be NULL) is not written, p / seed unused.
+int triad_preln_fwd(const void* res, const void* y, const float* w, const float* b, float eps, int M, int D, float p,
+                    unsigned seed, void* res_out, void* n_out, int n_is_f32, float* mean, float* rstd,
+                    hipStream_t stream) {
+  if (M <= 0 || D <= 0 || D % 256 || D > 1024 || !p_ok(p) || !(eps > 0.f && eps < __builtin_inff())) return TRIAD_EINVAL;
+  if (!ptr_ok(res, 8) || !opt_ok(y, 8) || !ptr_ok(w, 16) || !ptr_ok(b, 16) || !ptr_ok(n_out, n_is_f32 ? 16 : 8) ||
+      !(y ? ptr_ok(res_out, 8) : opt_ok(res_out, 8)) || !ptr_ok(mean, 4) || !ptr_ok(rstd, 4))
+    return TRIAD_EINVAL;
+  const float scale = 1.f / (1.f - p);
+  const dim3 grid((M + 3) / 4);
+#define PLN_F(NB)                                                                                                  \
+  if (D == NB * 256) {                                                                                             \
+    hipLaunchKernelGGL(preln_fwd_kernel<NB>, grid, dim3(256), 0, stream, (const bf16*)res, (const bf16*)y, w, b, eps, \
+                       M, seed, drop_thr(p), scale, (bf16*)res_out, n_out, n_is_f32, mean, rstd);                  \
+    TRIAD_CHECK_LAUNCH();                                                                                          \
+    return TRIAD_OK;                                                                                               \
+  }
+  PLN_F(1) PLN_F(2) PLN_F(3) PLN_F(4)
+#undef PLN_F
+  return TRIAD_EINVAL;
+}
+
+int triad_preln_bwd_blocks(int M) { return triad_dropaddln_bwd_blocks(M); }
+
+// dres = bf16(dz + LN'(dn) at z) (dz bf16, dn bf16 or fp32 (dn_is_f32); either may be NULL, not both),
+// dy = dropout'(dres) (NULL when the forward had no y); part: blocks x 2 x D fp32 dgamma / dbeta
+// partials (triad_preln_bwd_blocks(M) blocks; zeros without dn).
+int triad_preln_bwd(const void* dz, const void* dn, int dn_is_f32, const void* z, const float* mean, const float* rstd,
+                    const float* w, int M, int D, float p, unsigned seed, void* dres, void* dy, float* part,
+                    hipStream_t stream) {
+  if (M <= 0 || D <= 0 || D % 256 || D > 1024 || !p_ok(p) || (!dz && !dn)) return TRIAD_EINVAL;
+  if (!opt_ok(dz, 8) || !opt_ok(dn, dn_is_f32 ? 16 : 8) || !ptr_ok(z, 8) || !ptr_ok(mean, 4) || !ptr_ok(rstd, 4) ||
+      !ptr_ok(w, 16) || !ptr_ok(dres, 8) || !opt_ok(dy, 8) || !ptr_ok(part, 4))
+    return TRIAD_EINVAL;
+  const float scale = 1.f / (1.f - p);
+  const dim3 grid(triad_preln_bwd_blocks(M));
+#define PLN_B(NB)                                                                                                  \
+  if (D == NB * 256) {                                                                                             \
+    hipLaunchKernelGGL(preln_bwd_kernel<NB>, grid, dim3(256), 0, stream, (const bf16*)dz, dn, dn_is_f32,            \
+                       (const bf16*)z, mean, rstd, w, M, seed, drop_thr(p), scale, (bf16*)dres, (bf16*)dy, part);  \
+    TRIAD_CHECK_LAUNCH();                                                                                          \
+    return TRIAD_OK;                                                                                               \
+  }
+  PLN_B(1) PLN_B(2) PLN_B(3) PLN_B(4)
+#undef PLN_B
   return TRIAD_EINVAL;
 }
 

@@ -13,6 +13,12 @@ and dropout keep bits are regenerated from a counter hash instead of stored. Mod
 parameters and state-dict keys are unchanged (the encoder's forward is swapped per instance);
 anything outside training-mode bf16 autocast on the GPU runs the stock transformers code.
 
+HuBERT-large (`do_stable_layer_norm`, HubertEncoderStableLayerNorm) is pre-LN: its residual stream is
+bf16 under autocast and each LayerNorm feeds only its branch. Its residual steps run on
+triad_preln_fwd / _bwd (drop_add_norm, fused_stable_layer, _stable_encoder_forward below): the add
+that produces the stream and the LayerNorm of the next consumer in one row pass, the stream's and the
+LayerNorm's gradients added in fp32 in one backward pass.
+
 Numerics: same operation order and roundings as the autocast chain; the dropout masks are drawn
 from the hash instead of torch's Philox stream (same distribution, p to 1.5e-5), so parity
 tests pin the kernels against torch on the SAME masks (triad_dropout_keep).
@@ -233,15 +239,144 @@ def _encoder_forward(self, hidden_states, attention_mask=None, output_attentions
     return BaseModelOutput(last_hidden_state=res)
 
 
+# ---- stable layer norm (pre-LN) encoder: HubertEncoderStableLayerNorm, HuBERT-large ----
+# Per layer  r1 = res + dropout(attn(LN1(res)));  r2 = r1 + dropout(fc2(dropout(gelu(fc1(LN2(r1))))))
+# and one LayerNorm after the last layer. Under bf16 autocast the residual stream is bf16 (the fp32
+# LayerNorm output feeds only the branch), so each residual step is triad_preln_fwd: the add that
+# produces the stream and the LayerNorm that FOLLOWS it (the next consumer's), in one row pass.
+
+class _DropAddNorm(torch.autograd.Function):
+    """(res_out, n) = (z, LN(z)), z = bf16(res + dropout(y)); res, y bf16 [..., D] (y None: z = res),
+    n bf16 or fp32 (out_f32). Saves z, w, mean, rstd -- neither res nor y; the backward takes either
+    incoming gradient as None and adds the stream's gradient to the LayerNorm's in fp32."""
+
+    @staticmethod
+    def forward(ctx, res, y, w, b, eps, p, seed, out_f32):
+        D = res.shape[-1]
+        M = res.numel() // D
+        dev = res.device
+        if not (res.dtype == torch.bfloat16 and (y is None or (y.dtype == torch.bfloat16 and y.shape == res.shape))
+                and w.dtype == b.dtype == torch.float32 and w.numel() == b.numel() == D):
+            raise TypeError(f"drop_add_norm: res {res.dtype} {tuple(res.shape)}, y "
+                            f"{None if y is None else (y.dtype, tuple(y.shape))}, w {w.dtype}")
+        res, y, w, b = _dense(res, 8), _dense(y, 8), _dense(w, 16), _dense(b, 16)
+        z = res if y is None else torch.empty_like(res)
+        n = torch.empty(res.shape, dtype=torch.float32 if out_f32 else torch.bfloat16, device=dev)
+        mean = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd = torch.empty(M, dtype=torch.float32, device=dev)
+        call("triad_preln_fwd", ptr(res), ptr(y), ptr(w), ptr(b), eps, M, D, p, seed, None if y is None else ptr(z),
+             ptr(n), int(out_f32), ptr(mean), ptr(rstd), stream_ptr(dev))
+        ctx.save_for_backward(z, w, mean, rstd)
+        ctx.meta = (p, seed, y is not None, out_f32)
+        ctx.set_materialize_grads(False)
+        return (z if y is not None else z.view_as(z)), n
+
+    @staticmethod
+    def backward(ctx, dz, dn):
+        if dz is None and dn is None:
+            return (None,) * 8
+        z, w, mean, rstd = ctx.saved_tensors
+        p, seed, has_y, out_f32 = ctx.meta
+        D = z.shape[-1]
+        M = z.numel() // D
+        dev = z.device
+        if dz is not None:
+            dz = _dense(dz.to(torch.bfloat16), 8)
+        if dn is not None:
+            dn = _dense(dn.to(torch.float32 if out_f32 else torch.bfloat16), 16)
+        if any(g is not None and g.shape != z.shape for g in (dz, dn)):
+            raise TypeError("drop_add_norm backward: unexpected gradient layout")
+        dres = torch.empty_like(z)
+        dy = torch.empty_like(z) if has_y else None
+        nb = call("triad_preln_bwd_blocks", M)
+        part = torch.empty(nb * 2 * D, dtype=torch.float32, device=dev)
+        st = stream_ptr(dev)
+        call("triad_preln_bwd", ptr(dz), ptr(dn), int(out_f32), ptr(z), ptr(mean), ptr(rstd), ptr(w), M, D, p, seed,
+             ptr(dres), ptr(dy), ptr(part), st)
+        gwb = torch.empty(2 * D, dtype=torch.float32, device=dev)
+        call("triad_sum_slabs", ptr(part), nb, 2 * D, None, 0, ptr(gwb), st, meta=dict(backbone=True))
+        return dres, dy, gwb[:D], gwb[D:], None, None, None, None
+
+
+def drop_add_norm(res, y, norm, p, seed, out_f32=False):
+    """(res_out, n): the bf16 stream res + dropout(y) and norm(res_out) as bf16, or fp32 (out_f32)."""
+    return _DropAddNorm.apply(res, y, norm.weight, norm.bias, norm.eps, p, seed, out_f32)
+
+
+def fused_stable_layer(layer, res, nb, next_norm, seeds, last):
+    """One HubertEncoderLayerStableLayerNorm on (bf16 stream, bf16 layer_norm(stream)) -> (stream,
+    next_norm(stream)): next_norm is the layer_norm of the next layer that executes, or after the
+    last one the encoder's, whose output is fp32 (last). Every tensor has exactly one consumer, so
+    autograd never sums residual gradients in bf16."""
+    p_h = layer.dropout.p if layer.training else 0.0
+    ff = layer.feed_forward
+    p_a = ff.intermediate_dropout.p if layer.training else 0.0
+    p_o = ff.output_dropout.p if layer.training else 0.0
+    a = self_attention(layer.attention, nb)
+    r1, n1b = drop_add_norm(res, a, layer.final_layer_norm, p_h, seeds())
+    v = gelu_drop(ff.intermediate_dense(n1b), p_a, seeds())
+    f = ff.output_dense(v)
+    return drop_add_norm(r1, f, next_norm, p_o, seeds(), out_f32=last)
+
+
+# Gate of the fused stable-LN path (installed either way; False = the stock loop runs). The rule, as for
+# attention.LONG_ROUTE: on by default only if the encoder's forward + backward is faster than stock by
+# more than the measured run-to-run spread at B = 32 AND B = 8 (tools/audio_large_time.py). Measured with
+# rounds of 30 passes (DESIGN.md section 4b, profiles/preln_time.log): B = 32 62.6 against 76.6 ms, B = 8
+# 29.7 against 31.6 ms with spreads of 2.0 % / 1.4 % -- ahead by more than the spread at both, so it is on.
+# (Rounds of 3 and 10 passes, windows of 0.1 - 0.3 s at B = 8, had spreads of 9 - 17 % there.)
+STABLE_ROUTE = True
+
+
+def _stable_ok(enc, hidden_states, attention_mask, output_attentions, output_hidden_states):
+    return (STABLE_ROUTE and _fused_ok(enc, hidden_states, attention_mask, output_attentions, output_hidden_states)
+            and hidden_states.dtype == torch.bfloat16 and not getattr(enc, "gradient_checkpointing", False)
+            and all(getattr(layer, "adapter_layer", None) is None for layer in enc.layers))
+
+
+def layerdrop_plan(enc):
+    """The layers this call executes: one torch.rand([]) per layer in layer order, as the stock loop
+    draws them (the same CPU generator stream), all drawn before the first layer runs."""
+    keep = []
+    for layer in enc.layers:
+        dropout_probability = torch.rand([])
+        if not (enc.training and dropout_probability < enc.config.layerdrop):
+            keep.append(layer)
+    return keep
+
+
+def _stable_encoder_forward(self, hidden_states, attention_mask=None, output_attentions=False,
+                            output_hidden_states=False, return_dict=True):
+    """HubertEncoderStableLayerNorm.forward with the fused layers; same pre-layer steps (no LayerNorm
+    there) and LayerDrop decisions; last_hidden_state is the encoder norm's fp32 output."""
+    if not _stable_ok(self, hidden_states, attention_mask, output_attentions, output_hidden_states):
+        return self._triad_stock_forward(hidden_states, attention_mask=attention_mask,
+                                         output_attentions=output_attentions,
+                                         output_hidden_states=output_hidden_states, return_dict=return_dict)
+    from transformers.modeling_outputs import BaseModelOutput
+    position_embeddings = self.pos_conv_embed(hidden_states)
+    hidden_states = hidden_states + position_embeddings
+    res = self.dropout(hidden_states)
+    layers = layerdrop_plan(self)
+    norms = [layer.layer_norm for layer in layers] + [self.layer_norm]
+    res, n = drop_add_norm(res, None, norms[0], 0.0, 0, out_f32=not layers)
+    for i, layer in enumerate(layers):
+        res, n = fused_stable_layer(layer, res, n, norms[i + 1], self._triad_seeds, i == len(layers) - 1)
+    if not return_dict:
+        return (n,)
+    return BaseModelOutput(last_hidden_state=n)
+
+
 def install_fused_encoder(hubert):
-    """Swap the post-LN HubertEncoder's forward for the fused one (stable-LN encoders, e.g.
-    HuBERT-large, keep the stock code)."""
-    from transformers.models.hubert.modeling_hubert import HubertEncoder
+    """Swap the HubertEncoder's (post-LN) or HubertEncoderStableLayerNorm's (pre-LN, HuBERT-large)
+    forward for the fused one, per instance."""
+    from transformers.models.hubert.modeling_hubert import HubertEncoder, HubertEncoderStableLayerNorm
     enc = hubert.encoder
-    if type(enc) is HubertEncoder and not hasattr(enc, "_triad_stock_forward"):
+    fwd = {HubertEncoder: _encoder_forward, HubertEncoderStableLayerNorm: _stable_encoder_forward}.get(type(enc))
+    if fwd is not None and not hasattr(enc, "_triad_stock_forward"):
         enc._triad_stock_forward = enc.forward
         enc._triad_seeds = _Seeds()
-        enc.forward = types.MethodType(_encoder_forward, enc)
+        enc.forward = types.MethodType(fwd, enc)
     return hubert
 
 
