@@ -288,8 +288,13 @@ int triad_gemm_bf16_tiles(const void* A, long long lda, int a_kcontig, const voi
  *   rowgemm_bias: C = bf16(A W^T + bias) (projection2 from ln in HBM);
  *   ln_bwd: dln = bf16(dy W2) (W2p = triad_bfrag_pack16(W2, 16, 1, .)), dy1 = bf16(rstd (g -
  *           mean(g) - xh mean(g xh))), g = dln gamma, and part [panels][3][512] column sums of
- *           dln xh (dgamma), dln (dbeta), dy1 (db1) per panel (reduce with triad_sum_slabs).
- * Biases are the bf16 vectors autocast adds (b1, b2, bias: bf16 [512]); gamma / beta fp32. */
+ *           dln xh (dgamma), dln (dbeta), dy1 (db1) per panel (reduce with triad_sum_slabs). Only
+ *           rows < M of dy, y1, mean and rstd are read: the pad rows of dy1 are zeros and the
+ *           partials hold nothing from a pad row, whatever those rows of y1 / mean / rstd hold.
+ * Biases are the bf16 vectors autocast adds (b1, b2, bias: bf16 [512]); gamma / beta fp32.
+ * TRIAD_EINVAL before any launch: a NULL pointer, M <= 0, K <= 0 or K % 32, lda < K, lda % 8,
+ * bstride % 8, n_per <= 0; h / A / dy, the packed weights, ln_bwd's y1 and part not 16-byte aligned;
+ * an output (y1, ln, y, C, dy1) not 8-byte aligned; eps negative or not finite. */
 int triad_wpack(const void* W, int K, void* Bp, hipStream_t stream);
 int triad_wpack2(const void* W1, int K1, void* Bp1, const void* W2, int K2, void* Bp2, hipStream_t stream);
 int triad_rowpanel_count(long long M);
@@ -316,17 +321,22 @@ int triad_similarity_maps(const void* f1, const void* f2, int B, int N1, int N2,
 
 /* LayerNorm(512) forward of the library-GEMM projection head (model.py:68/116/326 under
  * autocast): ln = bf16((y1 - mean) rstd gamma + beta) over bf16 y1 [M][512], fp32 statistics
- * (biased variance, eps) kept in mean / rstd [M]. */
+ * (biased variance, eps) kept in mean / rstd [M]. TRIAD_EINVAL for M <= 0, a NULL pointer, y1 or
+ * ln not 16-byte aligned. */
 int triad_ln_fwd(const void* y1, int M, const float* gamma, const float* beta, float eps, void* ln, float* mean,
                  float* rstd, hipStream_t stream);
 
 /* Its backward from a bf16 dln: dy1 (bf16) and per-block column partials [nblocks][3][512] of
- * dgamma, dbeta, db1 (= column sums of dy1), reduced by triad_sum_slabs. */
+ * dgamma, dbeta, db1 (= column sums of dy1), reduced by triad_sum_slabs (a block without rows
+ * writes zeros). TRIAD_EINVAL for M <= 0, a NULL pointer, dln / y1 / dy1 not 16-byte aligned,
+ * nblocks outside 1 .. 16,777,215 (256-thread blocks within a grid dimension's 2^32 - 1 threads). */
 int triad_ln_bwd3(const void* dln, const void* y1, const float* mean, const float* rstd, const float* gamma, int M,
                   void* dy1, float* part, int nblocks, hipStream_t stream);
 
 /* out[c] = alpha * sum_r X[r][c] over bf16 X [rows][ld] (cols % 8 == 0), fp32 or bf16 out, at HBM rate:
- * row slices x 8-column 16-byte loads, partials in part (triad_colsum_splits(rows, cols) * cols floats). */
+ * row slices x 8-column 16-byte loads, partials in part (triad_colsum_splits(rows, cols) * cols floats).
+ * TRIAD_EINVAL for a NULL pointer, X not 16-byte aligned, rows <= 0, cols <= 0 or cols % 8, ld % 8,
+ * ld < cols. */
 int triad_colsum_splits(long long rows, int cols);
 int triad_colsum(const void* X, long long rows, int cols, long long ld, float* part, float alpha, int out_bf16,
                  void* out, hipStream_t stream);
@@ -336,12 +346,14 @@ int triad_colsum(const void* X, long long rows, int cols, long long ld, float* p
  * gradients of the heads and backbones, SpecAugment's masked_spec_embed (beside concurrent
  * streams' GEMMs, plain-load column sums returned disturbed values; reference:
  * autograd's bias gradients of model.py:32-34 / 81-83 / 253-255 and the backbones' Linear layers).
- * part: triad_colsum_dma_splits(rows, cols) * cols floats. */
+ * part: triad_colsum_dma_splits(rows, cols) * cols floats, 16-byte aligned (the second pass reads it
+ * by LDS-DMA). TRIAD_EINVAL as triad_colsum, and for a part that is not 16-byte aligned. */
 int triad_colsum_dma_splits(long long rows, int cols);
 int triad_colsum_dma(const void* X, long long rows, int cols, long long ld, float* part, float alpha, int out_bf16,
                      void* out, hipStream_t stream);
 
-/* out[e] = alpha * sum_i slabs[i][e] (alpha may be NULL = 1), fp32 or bf16 out. */
+/* out[e] = alpha * sum_i slabs[i][e] (alpha may be NULL = 1), fp32 or bf16 out. TRIAD_EINVAL for
+ * nslab <= 0, n <= 0, slabs or out NULL. */
 int triad_sum_slabs(const float* slabs, int nslab, long long n, const float* alpha, int out_bf16, void* out,
                     hipStream_t stream);
 

@@ -292,13 +292,19 @@ __global__ __launch_bounds__(256) void colsum_dma_kernel(const void* __restrict_
   }
 }
 
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+// HIP launches at most 2^32 - 1 threads per grid dimension: the limit on a grid of 256-thread blocks
+constexpr long long MAX_BLOCKS_256 = 0xffffffffLL / 256;
+
 }  // namespace
 
 extern "C" {
 
 int triad_ln_fwd(const void* y1, int M, const float* gamma, const float* beta, float eps, void* ln, float* mean,
                  float* rstd, hipStream_t stream) {
-  if (M <= 0) return TRIAD_EINVAL;
+  // rows are read and written 16 bytes per lane
+  if (M <= 0 || !y1 || !gamma || !beta || !ln || !mean || !rstd || misaligned16(y1) || misaligned16(ln))
+    return TRIAD_EINVAL;
   const int nb = (M + 3) / 4 < 4096 ? (M + 3) / 4 : 4096;
   hipLaunchKernelGGL(ln_fwd_kernel, dim3(nb), dim3(256), 0, stream, (const bf16*)y1, M, gamma, beta, eps, (bf16*)ln,
                      mean, rstd);
@@ -308,7 +314,9 @@ int triad_ln_fwd(const void* y1, int M, const float* gamma, const float* beta, f
 
 int triad_ln_bwd3(const void* dln, const void* y1, const float* mean, const float* rstd, const float* gamma, int M,
                   void* dy1, float* part, int nblocks, hipStream_t stream) {
-  if (M <= 0 || nblocks <= 0) return TRIAD_EINVAL;
+  if (M <= 0 || nblocks <= 0 || nblocks > MAX_BLOCKS_256 || !dln || !y1 || !mean || !rstd || !gamma || !dy1 || !part ||
+      misaligned16(dln) || misaligned16(y1) || misaligned16(dy1))
+    return TRIAD_EINVAL;
   hipLaunchKernelGGL(ln_bwd3_kernel, dim3(nblocks), dim3(256), 0, stream, (const bf16*)dln, (const bf16*)y1, mean,
                      rstd, gamma, M, (bf16*)dy1, part);
   TRIAD_CHECK_LAUNCH();
@@ -317,7 +325,7 @@ int triad_ln_bwd3(const void* dln, const void* y1, const float* mean, const floa
 
 int triad_sum_slabs(const float* slabs, int nslab, long long n, const float* alpha, int out_bf16, void* out,
                     hipStream_t stream) {
-  if (nslab <= 0 || n <= 0) return TRIAD_EINVAL;
+  if (nslab <= 0 || n <= 0 || !slabs || !out) return TRIAD_EINVAL;
   // many slabs of a short vector (bias / LayerNorm column partials: <= 3 x 512 columns over up to
   // 1,024 slabs): 16 slab lanes per element. Long vectors (the split-K weight-gradient slabs,
   // 262,144-393,216 elements x 32 slabs) stream with one element per thread instead: the 64-column
@@ -361,8 +369,9 @@ int triad_colsum_dma_splits(long long rows, int cols) {
 
 int triad_colsum_dma(const void* X, long long rows, int cols, long long ld, float* part, float alpha, int out_bf16,
                      void* out, hipStream_t stream) {
-  if (rows <= 0 || cols <= 0 || cols % 8 || ld % 8 || ld < cols || !part || !X || !out ||
-      ((uintptr_t)X & 15))
+  // part: the second pass reads it back by 16-byte LDS-DMA
+  if (rows <= 0 || cols <= 0 || cols % 8 || ld % 8 || ld < cols || !part || !X || !out || misaligned16(X) ||
+      misaligned16(part))
     return TRIAD_EINVAL;
   const int S = triad_colsum_dma_splits(rows, cols);
   long long per = (rows + S - 1) / S;
@@ -378,11 +387,13 @@ int triad_colsum_dma(const void* X, long long rows, int cols, long long ld, floa
 
 int triad_colsum(const void* X, long long rows, int cols, long long ld, float* part, float alpha, int out_bf16,
                  void* out, hipStream_t stream) {
-  if (rows <= 0 || cols <= 0 || cols % 8 || ld % 8 || ld < cols) return TRIAD_EINVAL;
+  if (rows <= 0 || cols <= 0 || cols % 8 || ld % 8 || ld < cols || !part || !X || !out || misaligned16(X))
+    return TRIAD_EINVAL;
   const int cg = cols / 8 < 256 ? cols / 8 : 256;
   const int S = triad_colsum_splits(rows, cols);
   const dim3 grid((cols / 8 + cg - 1) / cg, S);
   hipLaunchKernelGGL(colsum8_kernel, grid, dim3(256), 0, stream, (const bf16*)X, rows, cols, ld, cg, part);
+  TRIAD_CHECK_LAUNCH();
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((cols + 63) / 64), dim3(1024), 0, stream, part, S, (long long)cols,
                      (const float*)nullptr, alpha, out_bf16, out);
   TRIAD_CHECK_LAUNCH();

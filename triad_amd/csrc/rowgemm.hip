@@ -208,11 +208,14 @@ __global__ __launch_bounds__(512, 1) void rowpanel_kernel(RPArgs a) {
     // the panel's y1 rows, one 1 KB row per LDS-DMA piece (wave w: rows 16 w ..), 16-byte chunk c
     // of row r at chunk c ^ (r & 15): the epilogue's 8-byte reads (16 rows x one chunk per half
     // wave) are then conflict-free. One wait for all of it, instead of 16 dependent global loads
-    // per lane (SQ_WAIT_ANY 0.53 of this kernel's wave time with those, profiles/r05_projhead_pmc.txt)
+    // per lane (SQ_WAIT_ANY 0.53 of this kernel's wave time with those, profiles/r05_projhead_pmc.txt).
+    // A pad row (>= M) re-reads row M - 1 (a wave-uniform clamp): finite values whatever the pad
+    // rows of y1 hold, which the zeroed rstd of a pad row turns into xh = 0 below
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int r = 16 * wave + i;
-      glds16(a.y1 + (m0 + r) * RP_N + 8 * (lane ^ (r & 15)), lds + RP_Y1_OFF + r * RP_N);
+      const long long yr = m0 + r < a.M ? m0 + r : a.M - 1;
+      glds16(a.y1 + yr * RP_N + 8 * (lane ^ (r & 15)), lds + RP_Y1_OFF + r * RP_N);
     }
   }
 
@@ -387,9 +390,10 @@ __global__ __launch_bounds__(512, 1) void rowpanel_kernel(RPArgs a) {
     // dln = bf16(dy W2) (autocast's projection2 input gradient, packed: the accumulators die here);
     // LayerNorm backward in fp32: xh = (y1 - mean) rstd, g = dln gamma,
     // dy1 = bf16(rstd (g - mean(g) - xh mean(g xh))); column partials over the panel's rows:
-    // dgamma = sum dln xh, dbeta = sum dln, db1 = sum dy1. y1 / mean / rstd have the panel-padded
-    // row count and the forward wrote zeros in the pad rows (xh = 0, rstd = 0 there: dy1 and every
-    // partial get nothing from them) -- read unmasked (y1 from the LDS panel loaded after the k
+    // dgamma = sum dln xh, dbeta = sum dln, db1 = sum dy1. A pad row (>= M) takes dln = 0,
+    // mean = rstd = 0 and row M - 1's finite y1 (selected at the loads, no register more in the
+    // loops), so xh = 0 there and dy1 and every partial get nothing from it whatever the pad rows of
+    // y1 / mean / rstd hold: none of them is read (y1 from the LDS panel loaded after the k
     // loop). The scheduling fences keep hipcc from hoisting every row's reads at once (the live
     // state -- packed dln, row statistics, the 48 column partials -- then fits the register file
     // without spills).
@@ -413,8 +417,11 @@ __global__ __launch_bounds__(512, 1) void rowpanel_kernel(RPArgs a) {
     float mu[8], rs[8], s1[8], s2[8];
 #pragma unroll
     for (int rb = 0; rb < 8; ++rb) {
-      mu[rb] = a.mean[m0 + 16 * rb + l16];
-      rs[rb] = a.rstd[m0 + 16 * rb + l16];
+      const long long m = m0 + 16 * rb + l16;
+      const bool ok = m < a.M;
+      const long long sr = ok ? m : a.M - 1;   // a pad row: 0 / 0 whatever mean / rstd hold there
+      mu[rb] = ok ? a.mean[sr] : 0.f;
+      rs[rb] = ok ? a.rstd[sr] : 0.f;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the y1 panel (and mean / rstd) landed
     __syncthreads();
@@ -516,13 +523,20 @@ __global__ __launch_bounds__(512, 1) void rowpanel_kernel(RPArgs a) {
   }
 }
 
+bool rp_misaligned(const void* p, unsigned n) { return ((uintptr_t)p & (n - 1)) != 0; }
+
+// Every rule runs before any launch. A rows and the packed weight are read 16 bytes at a time
+// (LDS-DMA / bf16x8 loads), a row segment of an output is one 8-byte store.
 int rp_check(const void* A, long long M, int K, long long lda, long long n_per, long long bstride, const void* Bp,
              const void* out0) {
   if (!A || !Bp || !out0 || M <= 0 || K <= 0 || K % RP_K || lda < K || lda % 8 || n_per <= 0 || bstride % 8 ||
-      ((uintptr_t)A & 15))
+      rp_misaligned(A, 16) || rp_misaligned(Bp, 16) || rp_misaligned(out0, 8))
     return TRIAD_EINVAL;
   return TRIAD_OK;
 }
+
+// LayerNorm eps: finite and >= 0 (a NaN fails both comparisons)
+bool rp_bad_eps(float eps) { return !(eps >= 0.f && eps <= 3.402823466e38f); }
 
 }  // namespace
 
@@ -557,7 +571,8 @@ int triad_rowpanel_count(long long M) { return M > 0 ? (int)((M + RP_M - 1) / RP
 int triad_projhead_ln_fwd(const void* h, long long M, int H, long long lda, long long n_per, long long bstride,
                           const void* W1p, const void* b1, const float* gamma, const float* beta, float eps, void* y1,
                           void* ln, float* mean, float* rstd, hipStream_t stream) {
-  if (rp_check(h, M, H, lda, n_per, bstride, W1p, y1) || !b1 || !gamma || !beta || !ln || !mean || !rstd)
+  if (rp_check(h, M, H, lda, n_per, bstride, W1p, y1) || !b1 || !gamma || !beta || !ln || !mean || !rstd ||
+      rp_misaligned(ln, 8) || rp_bad_eps(eps))
     return TRIAD_EINVAL;
   RPArgs a{(const bf16*)h, lda, n_per, bstride, M, H, (const bf16*)W1p, (const bf16*)b1, gamma, beta, eps,
            (bf16*)y1, (bf16*)ln, mean, rstd, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -575,7 +590,7 @@ int triad_projhead_fwd(const void* h, long long M, int H, long long lda, long lo
                        const void* W2p, const void* b2, void* y1, void* ln, float* mean, float* rstd, void* y,
                        hipStream_t stream) {
   if (rp_check(h, M, H, lda, n_per, bstride, W1p, y1) || !b1 || !gamma || !beta || !ln || !mean || !rstd || !W2p ||
-      !b2 || !y)
+      !b2 || !y || rp_misaligned(ln, 8) || rp_misaligned(y, 8) || rp_misaligned(W2p, 16) || rp_bad_eps(eps))
     return TRIAD_EINVAL;
   RPArgs a{(const bf16*)h, lda, n_per, bstride, M, H, (const bf16*)W1p, (const bf16*)b1, gamma, beta, eps,
            (bf16*)y1, (bf16*)ln, mean, rstd, nullptr, nullptr, (const bf16*)W2p, (const bf16*)b2, (bf16*)y};
@@ -602,7 +617,9 @@ int triad_rowgemm_bias(const void* A, long long M, int K, long long lda, const v
 // triad_bfrag_pack16(W2, 16, 1, .) (Bt = W2 itself); y1 / mean / rstd from triad_projhead_ln_fwd.
 int triad_projhead_ln_bwd(const void* dy, long long M, const void* W2p, const void* y1, const float* mean,
                           const float* rstd, const float* gamma, void* dy1, float* part, hipStream_t stream) {
-  if (rp_check(dy, M, RP_N, RP_N, M, 0, W2p, dy1) || !y1 || !mean || !rstd || !gamma || !part) return TRIAD_EINVAL;
+  if (rp_check(dy, M, RP_N, RP_N, M, 0, W2p, dy1) || !y1 || !mean || !rstd || !gamma || !part ||
+      rp_misaligned(y1, 16) || rp_misaligned(part, 16))
+    return TRIAD_EINVAL;
   RPArgs a{(const bf16*)dy, RP_N, M, 0, M, RP_N, (const bf16*)W2p, nullptr, gamma, nullptr, 0.f,
            (bf16*)dy1, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), (const bf16*)y1, part,
            nullptr, nullptr, nullptr};
